@@ -10,7 +10,13 @@ A "step" = one pass of the hot path over one volume pair per rank:
   fwd : ModeT.forward incl. the final warp, no grad                                    [cfg 2]
 Inputs are resident in HBM before the timed region.  One JSON line on stdout (rank 0).
 
-roofline: the dominant kernel group (largest share of step time, found in an untimed profiled step) is
+A plain run sets up, warms up, chooses hipGraph replay or eager steps, times the K steps (each run's timed steps start from
+the seeded weights and optimizer state) and prints the headline line.  --full adds everything else below: the per-op
+profile, roofline / roofline_top, host enqueue times, the all-reduce probe, the side legs in `extra` and cpu_baseline.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (<= 60 MB in all; a larger array as a
+fixed seeded sample): train: loss, sim, reg, grad (flat gradient), params (flat parameters after the update); fwd: y_moved, flow.
+
+roofline (--full): the dominant kernel group (largest share of step time, found in an untimed profiled step) is
 timed live with HIP events on the launch stream during the K timed steps; achieved = its algorithmic
 FLOPs (or bytes) / its summed duration.  cpu_baseline: the CPU oracle (oracle/modet_torch.py, ATen-CPU,
 same op sequence as the reference's PyTorch-CPU path) on this host's cores, rank 0, N=1 only.
@@ -323,7 +329,7 @@ def operator_only(args, rank, local, world):
     ms = float(t)
     l1 = rows[0]
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # the plain-C restatement of the CUDA operator (oracle/modet_ref.c: ref_modet_fw / ref_modet_bw, fp64, one thread)
         # on a bounded sample -- the level-1 shape, 4 915 200 of the step's 5 768 400 voxel-heads -- scaled to the whole step
         import numpy as np
@@ -426,6 +432,22 @@ def cfg5_leg(dev, steps):
     return out
 
 
+def dump_outputs(out_dir, arrays, budget=60 * 10 ** 6):
+    """name -> tensor, written as out_dir/<name>.npy in float32 (float64 stays float64), smallest first; an array larger than
+    an even share of the budget left is written as its elements at a fixed seeded sample of flat indices"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        a = t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        share = budget // (len(items) - i) // a.itemsize
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+            log(f"[bench] {name}: {t.numel()} elements, writing a seeded sample of {share}")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        budget -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -442,8 +464,17 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the cfg-2 (forward+warp) and cfg-1 (CPU 64^3) side legs")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="train workload: replay forward+backward as one hipGraph in the timed region (auto = if capture succeeds)")
-    ap.add_argument("--breakdown", default="", help="write the per-op breakdown of one profiled step to this JSON file")
+    ap.add_argument("--breakdown", default="", help="with --full: write the per-op breakdown of one profiled step to this JSON file")
+    ap.add_argument("--full", action="store_true", help="also the per-op profile, roofline, host enqueue times, all-reduce "
+                                                         "probe, side legs and CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.breakdown and not args.full:
+        ap.error("--breakdown needs --full")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload not in ("train", "fwd"):
+        ap.error("--dump-outputs is available for the train and fwd workloads")
     shape = tuple(int(s) for s in args.shape.split(","))
 
     from smilecode_amd import models, ops, synth
@@ -477,19 +508,24 @@ def main():
 
     def step():
         if args.workload == "train":
-            last["loss"] = trainer.train_step(mov, fix, epoch=0)[0]      # device scalar, read once after the timed region
+            last["out"] = trainer.train_step(mov, fix, epoch=0)          # device scalars, read once after the timed region
+            last["loss"] = last["out"][0]
         else:
-            trainer.infer(mov, fix)
+            last["out"] = trainer.infer(mov, fix)
 
     def barrier():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
 
-    # warmup (untimed); the last (up to three) warmup steps are profiled per op to find the dominant kernel group.  The
+    # the timed steps start from this state however many steps ran before them: a run's outputs depend on its arguments only
+    state = (trainer.fp.flat, trainer.m, trainer.v, trainer.vmax)
+    start = ([t.clone() for t in state], trainer.step)
+
+    # warmup (untimed); --full profiles the last (up to three) warmup steps per op to find the dominant kernel group.  The
     # per-family time is the MEDIAN over those steps: a single profiled step can contain a one-off stall (a 10 ms
     # hiccup inside a 35 us kernel was observed once) that would crown the wrong family.
-    nprof = max(1, min(3, args.warmup))       # --warmup 0 still gets one untimed profiled step
+    nprof = max(1, min(3, args.warmup)) if args.full else 0       # --full --warmup 0 still gets one untimed profiled step
     for _ in range(max(args.warmup - nprof, 0)):
         step()
     torch.cuda.synchronize()
@@ -513,7 +549,7 @@ def main():
         d["pflops"] += v["flops"] * piece_products(k)
         d["tags"].add(k)
     dominant = max(fams, key=lambda k: fams[k]["ms"]) if fams else None
-    if rank == 0:
+    if rank == 0 and args.full:
         tot = sum(v["ms"] for v in breakdown.values())
         log(f"[bench] per-op breakdown of one {args.workload} step (HIP events, median of {nprof} profiled steps, sum {tot:.3f} ms):")
         for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1]["ms"]):
@@ -529,13 +565,15 @@ def main():
 
     # host-side cost of one step (Python + autograd + ~500 launches), measured as the time to enqueue a step on an
     # idle GPU: the device runs behind the host as long as this stays below ms_per_step
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    step()
-    host_ms = (time.perf_counter() - t0) * 1e3
-    torch.cuda.synchronize()
-    if rank == 0:
-        log(f"[bench] host enqueue time of one step: {host_ms:.2f} ms")
+    host_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        step()
+        host_ms = (time.perf_counter() - t0) * 1e3
+        torch.cuda.synchronize()
+        if rank == 0:
+            log(f"[bench] host enqueue time of one step: {host_ms:.2f} ms")
 
     # hipGraph: forward + losses + backward + gradient packing captured once, replayed per step (engine.Trainer.capture);
     # the all-reduce and the Adam kernel stay eager.  A replayed graph cannot carry per-kernel events, so the roofline leg
@@ -584,7 +622,7 @@ def main():
                     step()
                 torch.cuda.synchronize()
     host_graph_ms = None
-    if graphed:
+    if graphed and args.full:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         step()
@@ -593,10 +631,14 @@ def main():
         if rank == 0:
             log(f"[bench] hipGraph replay: host enqueue time of one step {host_graph_ms:.2f} ms")
 
-    # timed region: exactly K steps.  Eager: only the dominant group carries events.  Graph: no events inside.
+    for t, t_start in zip(state, start[0]):
+        t.copy_(t_start)
+    trainer.step = start[1]
+
+    # timed region: exactly K steps.  Eager --full: only the dominant group carries events.  Graph: no events inside.
     tsel = ops.KernelTimer(select=set(fams[dominant]["tags"]) if dominant else set())
     barrier()
-    if not graphed:
+    if args.full and not graphed:
         ops.set_kernel_timer(tsel)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -615,8 +657,14 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:            # before anything below runs another step
+        if args.workload == "train":
+            names = ("loss", "sim", "reg")
+            dump_outputs(args.dump_outputs, dict(zip(names, last["out"]), grad=trainer.fp.grad, params=trainer.fp.flat))
+        else:
+            dump_outputs(args.dump_outputs, dict(zip(("y_moved", "flow"), last["out"])))
     roof_steps, dt_eager = args.steps, None
-    if graphed:
+    if graphed and args.full:
         # roofline leg: the same K steps again, eager, with HIP events around every launch of the dominant kernel
         trainer.release_graph()
         for _ in range(2):
@@ -630,9 +678,9 @@ def main():
         dt_eager = time.perf_counter() - t0
         ops.set_kernel_timer(None)
 
-    ar_probe = allreduce_probe(trainer.fp.grad, world) if world > 1 else None     # after the timed region, every rank
+    ar_probe = allreduce_probe(trainer.fp.grad, world) if world > 1 and args.full else None     # after the timed region, every rank
     extra = {}
-    if world == 1 and args.workload == "train" and not args.no_extra:
+    if args.full and world == 1 and args.workload == "train" and not args.no_extra:
         # cfg 2 (forward + final warp, no grad) on the same pair, and the cfg-1 CPU leg (64^3 forward of the oracle)
         for _ in range(3):
             trainer.infer(mov, fix)
@@ -720,7 +768,10 @@ def main():
             "allreduce": ar_probe,
             "extra": extra,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if not args.full:                                              # the headline alone
+            for k in ("roofline", "roofline_top", "host_enqueue_ms_per_step", "eager", "allreduce", "extra"):
+                del out[k]
+        elif world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(shape, args.workload)
             except Exception as e:                                     # the GPU number must still be reported

@@ -49,12 +49,17 @@ NO_PACKED_FP32 = {"na.hip": ("na_bwd_kernel", "na_bwd_march_kernel"), "warp.hip"
 
 def _check_no_packed_fp32(hipcc: str, src: str, kernels) -> None:
     import re
-    asm = os.path.join(OBJ_DIR, os.path.basename(src).replace(".hip", ".s"))
-    r = subprocess.run([hipcc] + FLAGS + ["--cuda-device-only", "-S", src, "-o", asm], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc -S failed: %s\n%s" % (src, r.stderr))
+    import tempfile
+    # the assembly goes to a scratch file: it names a per-path compilation-unit id, so a copy kept in the tree would change
+    # with every checkout it is built in
+    with tempfile.TemporaryDirectory() as tmp:
+        asm = os.path.join(tmp, os.path.basename(src).replace(".hip", ".s"))
+        r = subprocess.run([hipcc] + FLAGS + ["--cuda-device-only", "-S", src, "-o", asm], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("hipcc -S failed: %s\n%s" % (src, r.stderr))
+        lines = open(asm).read().splitlines()
     cur, bad = None, {}
-    for line in open(asm):
+    for line in lines:
         m = re.match(r"^(_Z\w+):", line)
         if m:
             cur = m.group(1)

@@ -19,5 +19,5 @@ fw=$(find /tmp/prof_w -name "*counter_collection.csv" | head -1)
 python $R/tools/pmc_traffic.py $ff $fw $OUT/pmc_traffic.json $OUT/${TAG}_pmc_traffic_by_kernel.csv
 cd $R
 cp $OUT/pmc_traffic.json $R/profiles/pmc_traffic.json      # bench.py reads roofline.traffic from here
-timeout 400 python bench.py --breakdown $OUT/${TAG}_breakdown_train_160x192x160.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout 400 python bench.py --full --breakdown $OUT/${TAG}_breakdown_train_160x192x160.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 cat $OUT/${TAG}_bench.json
