@@ -362,6 +362,54 @@ class Correlation3D(nn.Module):
         return ops.correlation3d(ops.to_channels_last(mov.contiguous()), ops.to_channels_last(fix.contiguous()))
 
 
+def unsupported_config(in_channel=1, channels=4, head_dim=6, num_heads=(8, 4, 2, 1, 1), act_dtype=torch.float32):
+    """None if every kernel on ModeT's path accepts this configuration, else a message naming the first argument a kernel
+    would refuse and the kernel's limit (ModeT.__init__ raises it instead of letting a launch fail inside forward or backward).
+    Limits the library reports are asked for; the others are restated next to a pointer at the kernel's own check."""
+    heads = list(num_heads)
+    if len(heads) != 5 or any(int(h) != h or h < 1 for h in heads):
+        return f"num_heads = {num_heads}: five positive head counts, coarsest level first"
+    if in_channel < 1 or channels < 1:
+        return f"in_channel = {in_channel}, channels = {channels}: both must be >= 1"
+    for i in (3, 4):
+        # levels 2 and 1 add the attention's 3*heads-channel output straight onto the 3-channel flow: the reference itself
+        # fails there unless the level has one head (ModeT/models.py:397-412)
+        if heads[i] != 1:
+            return f"num_heads[{i}] = {heads[i]}: levels 2 and 1 add a 3*heads-channel field to the 3-channel flow, so it must be 1"
+    # the attention: the head-dimension-6 kernels or the generic ones (csrc/na.hip gen_hd_ok: a multiple of 8 up to 128)
+    if head_dim != 6 and not (head_dim % 8 == 0 and 8 <= head_dim <= 128):
+        return f"head_dim = {head_dim}: the attention kernels need head_dim 6 or a multiple of 8 up to 128"
+    L = ops._L()
+    for i in range(3):                  # the CWMs of levels 5, 4, 3
+        h = heads[i]
+        # the CWM's first conv 3h -> 6h carries the InstanceNorm statistics in its epilogue (modet_conv3d_stats_bytes is 0
+        # where it cannot: csrc/conv3d.hip conv_stats_ok), and the InstanceNorm kernels need 6h % 4 == 0 (csrc/norm_act.hip)
+        if L.modet_conv3d_stats_bytes(1, 8, 8, 8, 3 * h, 6 * h) == 0:
+            return f"num_heads[{i}] = {h}: the CWM InstanceNorm needs 6*heads % 4 == 0 and 6*heads <= 128"
+        # the CWM tail (softmax over the heads, weighted sum of the fields) is instantiated for 1, 2, 4 and 8 heads
+        # (csrc/warp.hip DISPATCH_HEADS)
+        if h not in (1, 2, 4, 8):
+            return f"num_heads[{i}] = {h}: the CWM tail kernel takes 1, 2, 4 or 8 heads"
+    for lvl in range(1, 6):
+        cin, dim = 2 ** lvl * channels, head_dim * heads[5 - lvl]
+        # csrc/proj_ln.hip: modet_proj_ln_fwd_t / modet_proj_ln_bwd refuse Cin % 4 != 0 or Cin > 128, and have kernels for
+        # dim 6, 12, 24 and 48 only
+        if cin % 4 != 0 or cin > 128:
+            return (f"channels = {channels}: the level-{lvl} projection has {cin} input channels; the projection kernels need "
+                    f"a multiple of 4 up to 128")
+        if dim not in (6, 12, 24, 48):
+            return (f"head_dim * num_heads[{5 - lvl}] = {dim}: the projection kernels produce 6, 12, 24 or 48 channels "
+                    f"(level {lvl})")
+    c = channels
+    for cin, cout in [(c, 2 * c), (2 * c, 2 * c)] + [(2 ** k * c, 2 ** (k + 1) * c) for k in range(1, 5)]:
+        if L.modet_conv3d_stats_bytes(1, 8, 8, 8, cin, cout) == 0:       # (the encoder's ConvInsBlocks: statistics epilogue)
+            return f"channels = {channels}: the encoder's ConvInsBlock {cin} -> {cout} has no statistics kernel"
+    # bf16 storage: csrc/conv3d_bf16.hip takes Cout % 8 == 0 and, beyond 8 input channels, Cin % 16 == 0
+    if act_dtype == torch.bfloat16 and c % 4 != 0:
+        return f"channels = {channels}: act_dtype=bfloat16 runs the encoder on bf16 conv kernels that need channels % 4 == 0"
+    return None
+
+
 class ModeT(nn.Module):
     """reference ModeT/models.py:338-412 (scale=None -> head_dim**-0.5)."""
 
@@ -382,6 +430,9 @@ class ModeT(nn.Module):
         self.fused_attention = fused_attention
         if act_dtype not in (torch.float32, torch.bfloat16):
             raise RuntimeError("ModeT: act_dtype must be torch.float32 or torch.bfloat16")
+        why = unsupported_config(in_channel, channels, head_dim, num_heads, act_dtype)
+        if why is not None:
+            raise RuntimeError("ModeT: " + why)
         self.act_dtype = act_dtype
         # bf16 storage of every level's warped features, q and k (ops.level_attention_bf16): head_dim 6 and the model's channel
         # counts only (the kernels the fused node runs), with the fused attention

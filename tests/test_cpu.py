@@ -177,6 +177,73 @@ def test_oracle_end_to_end_golden(orc):
         assert_close(got, ref.reshape(-1), atol=1e-12, rtol=1e-9, what=n)
 
 
+def test_oracle_end_to_end_golden_at_another_configuration(orc):
+    """the oracle against the reference at num_heads=[4,4,2,1,1], channels=2, scale=None (tests/golden/make_goldens_heads.py):
+    the GPU parity tests of non-default configurations compare the kernels with this oracle"""
+    from smilecode_amd import synth
+    g = gold("e2e_heads_4_4_2_c2.npz")
+    shape, heads, c, hd = tuple(int(v) for v in g["shape"]), [int(v) for v in g["num_heads"]], int(g["channels"]), int(g["head_dim"])
+    assert (shape, heads, c, hd) == ((32, 48, 32), [4, 4, 2, 1, 1], 2, 6)
+    s = int(g["stride"])
+    p = {n: T(v) for n, v in synth.make_weights(24, c, hd, heads).items()}
+    mov, fix = (T(a) for a in synth.make_pair(shape, 24))
+    with torch.no_grad():
+        loss, _, _, y, flow = orc.train_loss(p, mov, fix, heads, hd, None)
+    assert float(g["flow_absmax"]) > 1.0, "the fixture's flow must be non-trivial"
+    assert_close(flow.numpy().reshape(-1)[::s], g["flow"], atol=2e-6, rtol=0, what="flow (fixture is fp32-rounded)")
+    assert_close(y.numpy().reshape(-1)[::s], g["y_moved"], atol=2e-7, rtol=0, what="y_moved")
+    assert abs(float(loss) - float(g["loss"])) < 1e-12
+
+
+# ModeT(...) configurations: (kwargs, None if accepted, else a fragment of the refusal message)
+CONFIGS = [
+    ({}, None),
+    ({"num_heads": [2, 2, 2, 1, 1]}, None),
+    ({"num_heads": [4, 4, 2, 1, 1]}, None),
+    ({"num_heads": [8, 8, 8, 1, 1]}, None),
+    ({"num_heads": [2, 4, 8, 1, 1]}, None),
+    ({"scale": None}, None),
+    ({"scale": 0.25}, None),
+    ({"channels": 2}, None),
+    ({"in_channel": 2}, None),
+    ({"head_dim": 24, "num_heads": [2, 2, 2, 1, 1]}, None),
+    ({"channels": 2, "num_heads": [4, 4, 2, 1, 1]}, None),
+    ({"channels": 8}, "channels = 8: the level-5 projection has 256 input channels"),
+    ({"channels": 3}, "channels = 3: the level-1 projection has 6 input channels"),
+    ({"num_heads": [4, 2, 1, 1, 1]}, "num_heads[2] = 1: the CWM InstanceNorm needs 6*heads % 4 == 0"),
+    ({"num_heads": [3, 2, 2, 1, 1]}, "num_heads[0] = 3: the CWM InstanceNorm needs 6*heads % 4 == 0"),
+    ({"num_heads": [6, 4, 2, 1, 1]}, "num_heads[0] = 6: the CWM tail kernel takes 1, 2, 4 or 8 heads"),
+    ({"num_heads": [8, 4, 2, 2, 1]}, "num_heads[3] = 2: levels 2 and 1 add a 3*heads-channel field"),
+    ({"num_heads": [8, 4, 2, 1, 2]}, "num_heads[4] = 2: levels 2 and 1 add a 3*heads-channel field"),
+    ({"num_heads": [8, 4, 2, 1]}, "five positive head counts"),
+    ({"head_dim": 4}, "head_dim = 4: the attention kernels need head_dim 6 or a multiple of 8 up to 128"),
+    ({"head_dim": 8, "num_heads": [2, 2, 2, 1, 1]}, "head_dim * num_heads[4] = 8: the projection kernels produce 6, 12, 24 or 48"),
+    ({"channels": 2, "act_dtype": torch.bfloat16}, "act_dtype=bfloat16 runs the encoder on bf16 conv kernels"),
+]
+
+
+@pytest.mark.parametrize("kw,refusal", CONFIGS, ids=[str(i) for i in range(len(CONFIGS))])
+def test_constructor_accepts_or_refuses_each_configuration(kw, refusal):
+    """ModeT / ModeT_cu refuse up front what a kernel on their path would refuse (inside forward or only in backward
+    otherwise), with the argument and the limit in the message; an accepted configuration has the reference's parameter
+    names and shapes (synth.param_spec, the list tests/golden/make_goldens*.py check against the reference)"""
+    from smilecode_amd import models, synth
+    for cls in (models.ModeT, models.ModeT_cu):
+        if refusal is not None:
+            with pytest.raises(RuntimeError) as e:
+                cls((32, 48, 32), **kw)
+            assert refusal in str(e.value), str(e.value)
+            continue
+        m = cls((32, 48, 32), **kw)
+        spec = synth.param_spec(kw.get("channels", 4), kw.get("head_dim", 6), kw.get("num_heads", HEADS), kw.get("in_channel", 1))
+        assert [(n, tuple(p.shape)) for n, p in m.named_parameters()] == list(spec.items())
+        w = synth.make_weights(24, kw.get("channels", 4), kw.get("head_dim", 6), kw.get("num_heads", HEADS), kw.get("in_channel", 1))
+        models.load_numpy_weights(m, w)
+        hd = kw.get("head_dim", 6)
+        want = kw["scale"] if kw.get("scale") else (1 if cls is models.ModeT_cu and "scale" not in kw else hd ** -0.5)
+        assert all(getattr(m, f"mdt{i}").scale == want for i in range(1, 6))
+
+
 def test_oracle_adam_matches_torch_optim(orc):
     gen = torch.Generator().manual_seed(0)
     w = torch.randn(50, generator=gen).double()

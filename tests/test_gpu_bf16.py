@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.util import note as _note
+
 pytestmark = pytest.mark.gpu
 BF_ULP = 2.0 ** -8
 
@@ -690,13 +692,36 @@ def test_bf16_mode_with_another_head_layout_trains():
     model now keeps the bf16 conv chains and runs its levels on fp32 features."""
     from smilecode_amd import losses, models, synth
     shape = (32, 48, 32)
-    m = models.ModeT(shape, head_dim=6, num_heads=[4, 4, 2, 1, 1], scale=1, act_dtype=torch.bfloat16).cuda()
-    assert not m.level_bf16 and not m.encoder.features16
+    heads = [4, 4, 2, 1, 1]
+    w = synth.make_weights(24, 4, 6, heads)
     mov, fix = (torch.from_numpy(a).cuda() for a in synth.make_pair(shape, 24))
-    y, flow = m(mov, fix)
-    loss = losses.NCC_vxm()(fix, y) + losses.Grad3d(penalty="l2")(flow, fix)
-    loss.backward()
-    assert torch.isfinite(loss) and all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in m.parameters())
+    res = {}
+    for dtype in (torch.bfloat16, torch.float32):
+        m = models.ModeT(shape, head_dim=6, num_heads=heads, scale=1, act_dtype=dtype).cuda()
+        models.load_numpy_weights(m, w)
+        if dtype == torch.bfloat16:
+            assert not m.level_bf16 and not m.encoder.features16
+        y, flow = m(mov, fix)
+        loss = losses.NCC_vxm()(fix, y) + losses.Grad3d(penalty="l2")(flow, fix)
+        loss.backward()
+        assert torch.isfinite(loss) and all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in m.parameters())
+        res[dtype] = (flow.detach().double().cpu(), float(loss.detach()), {n: p.grad.double().cpu() for n, p in m.named_parameters()})
+    # the bf16 model against the fp32 one of the same layout, held to the bounds test_bf16_end_to_end_tolerances states
+    # against the reference's own autocast run (tests/golden/bf16_yardstick.json)
+    (f16, l16, g16), (f32, l32, g32) = res[torch.bfloat16], res[torch.float32]
+    ef = f16 - f32
+    keep = [n for n in g32 if float(g32[n].abs().max()) >= 1e-8]           # (conv biases under InstanceNorm: analytically 0)
+    gv, rv = torch.cat([g16[n].reshape(-1) for n in keep]), torch.cat([g32[n].reshape(-1) for n in keep])
+    r = {"flow_rms": float(ef.pow(2).mean().sqrt()), "flow_p999": float(ef.abs().flatten().kthvalue(int(0.999 * ef.numel())).values),
+         "loss_err": abs(l16 - l32), "grad_rel_l2": float((gv - rv).norm() / rv.norm()),
+         "grad_cos": float(F.cosine_similarity(gv, rv, 0)), "flow_absmax": float(f32.abs().max())}
+    for k, v in r.items():
+        _note(f"bf16_heads_4_4_2.{k}", v)
+    y = _yardstick(shape)
+    assert r["flow_absmax"] > 1.0, r
+    assert r["flow_rms"] <= 1.5 * y["flow_rms"] and r["flow_p999"] <= 1.5 * y["flow_p999"], (r, y)
+    assert r["loss_err"] <= 5e-3, r
+    assert r["grad_rel_l2"] <= 1.5 * y["grad_rel_l2"] and 1.0 - r["grad_cos"] <= 1.5 * (1.0 - y["grad_cos"]), (r, y)
 
 
 def test_bf16_staged_backward_matches_the_plain_one():

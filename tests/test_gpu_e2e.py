@@ -256,6 +256,200 @@ def test_forward_and_grads_vs_oracle_edge_shapes(shape, batch):
     assert worst < 5e-3, worst
 
 
+# ---- configurations other than the default ModeT(channels=4, head_dim=6, num_heads=[8,4,2,1,1]): each runs kernels the
+# default never reaches (generic projection pairs, two unpaired projection nodes per level, CWMs at other head counts,
+# the generic attention head dimension, four-channel level-1 features)
+def _cfg(kw):
+    return (kw.get("in_channel", 1), kw.get("channels", 4), kw.get("head_dim", 6), list(kw.get("num_heads", (8, 4, 2, 1, 1))))
+
+
+def _cfg_model(shape, kw, cls="ModeT", **extra):
+    from smilecode_amd import models, synth
+    in_channel, channels, head_dim, heads = _cfg(kw)
+    m = getattr(models, cls)(shape, in_channel=in_channel, channels=channels, head_dim=head_dim, num_heads=heads,
+                             scale=kw.get("scale", 1.0), **extra).cuda()
+    w = synth.make_weights(24, channels, head_dim, heads, in_channel)
+    models.load_numpy_weights(m, w)
+    return m, w
+
+
+def _worst_grad(named_grads, g64):
+    """max over parameter tensors of max|grad - ref| / max|ref| (tensors whose reference is analytically zero skipped)"""
+    worst, at = 0.0, ""
+    for n, g in named_grads:
+        ref = g64[n]
+        if float(ref.abs().max()) < 1e-8:
+            continue                                          # (a conv bias under InstanceNorm)
+        e = float((g.double().cpu() - ref).abs().max()) / float(ref.abs().max())
+        if e > worst:
+            worst, at = e, n
+    return worst, at
+
+
+OTHER_CONFIGS = [
+    ("heads_2_2_2", {"num_heads": [2, 2, 2, 1, 1]}, (32, 48, 32), 1),
+    ("heads_4_4_2", {"num_heads": [4, 4, 2, 1, 1]}, (48, 64, 48), 1),
+    ("heads_8_8_8", {"num_heads": [8, 8, 8, 1, 1]}, (32, 48, 32), 2),
+    ("heads_2_4_8", {"num_heads": [2, 4, 8, 1, 1]}, (48, 64, 48), 1),
+    ("scale_none", {"scale": None}, (32, 48, 32), 1),
+    ("scale_0.25", {"scale": 0.25}, (48, 64, 48), 1),
+    ("channels_2", {"channels": 2}, (48, 64, 48), 2),
+    ("head_dim_24", {"head_dim": 24, "num_heads": [2, 2, 2, 1, 1], "scale": None}, (32, 48, 32), 1),
+    ("heads_4_4_2_channels_2", {"num_heads": [4, 4, 2, 1, 1], "channels": 2, "scale": None}, (32, 48, 32), 1),
+]
+
+
+@pytest.mark.parametrize("tag,kw,shape,batch", OTHER_CONFIGS, ids=[c[0] for c in OTHER_CONFIGS])
+def test_other_configuration_vs_oracle(tag, kw, shape, batch):
+    """forward, NCC + Grad3d loss and every parameter gradient of a non-default configuration against the fp64 oracle, with
+    the bounds of test_forward_and_grads_vs_oracle_edge_shapes; the [4,4,2,1,1] / channels=2 model also against the
+    reference's own fp64 output (tests/golden/e2e_heads_4_4_2_c2.npz)"""
+    from oracle import modet_torch as orc
+    from smilecode_amd import losses, synth
+    _, _, head_dim, heads = _cfg(kw)
+    m, w = _cfg_model(shape, kw)
+    mov_np, fix_np = synth.make_pair(shape, 24, batch)
+    p64 = {n: torch.from_numpy(v).double().requires_grad_(True) for n, v in w.items()}
+    loss64, _, _, y64, f64 = orc.train_loss(p64, torch.from_numpy(mov_np).double(), torch.from_numpy(fix_np).double(), heads,
+                                            head_dim, kw.get("scale", 1.0))
+    g64 = dict(zip(p64, torch.autograd.grad(loss64, list(p64.values()))))
+    mov, fix = torch.from_numpy(mov_np).cuda(), torch.from_numpy(fix_np).cuda()
+    y, flow = m(mov, fix)
+    assert float(f64.abs().max()) > 1.0, "the weights must give a non-trivial flow"
+    ef = assert_close(np64(flow), f64.detach().numpy(), atol=2e-3, rtol=0, what="flow (voxels)")
+    ey = assert_close(np64(y), y64.detach().numpy(), atol=5e-4, rtol=0, what="y_moved")
+    loss = losses.NCC_vxm()(fix, y) + losses.Grad3d(penalty="l2")(flow, fix)
+    el = abs(float(loss.detach()) - float(loss64.detach()))
+    assert el < 2e-6, el
+    loss.backward()
+    worst, at = _worst_grad(((n, p.grad) for n, p in m.named_parameters()), g64)
+    _note(f"config[{tag}].flow_maxerr_voxels", ef)
+    _note(f"config[{tag}].y_moved_maxerr", ey)
+    _note(f"config[{tag}].loss_err", el)
+    _note(f"config[{tag}].grad_worst_rel_to_max", worst)
+    assert worst < 5e-3, (worst, at)
+    if tag == "heads_4_4_2_channels_2":
+        g = gold("e2e_heads_4_4_2_c2.npz")
+        s = int(g["stride"])
+        _note(f"config[{tag}].flow_maxerr_vs_reference", assert_close(np64(flow).reshape(-1)[::s], g["flow"], atol=2e-3, rtol=0,
+                                                                      what="flow vs reference fp64"))
+        assert_close(np64(y).reshape(-1)[::s], g["y_moved"], atol=5e-4, rtol=0, what="y_moved vs reference fp64")
+        assert abs(float(loss.detach()) - float(g["loss"])) < 2e-6
+
+
+def test_two_input_channels_vs_oracle():
+    """in_channel=2 (two image channels; the ConvBlock 2 -> 4 is not a conv_c1 specialisation): the forward, and the gradient
+    of a scalar of the flow alone -- Grad3d + <flow, r> -- since NCC takes one channel"""
+    from oracle import modet_torch as orc
+    from smilecode_amd import losses, synth
+    shape, kw = (32, 48, 32), {"in_channel": 2}
+    m, w = _cfg_model(shape, kw)
+    a, b = synth.make_pair(shape, 24, 2)
+    mov_np, fix_np = np.concatenate([a[:1], a[1:]], 1), np.concatenate([b[:1], b[1:]], 1)    # (1, 2, D, H, W)
+    r = torch.from_numpy(synth.make_flow(shape, 5, 1.0))
+    p64 = {n: torch.from_numpy(v).double().requires_grad_(True) for n, v in w.items()}
+    y64, f64 = orc.modet_forward(p64, torch.from_numpy(mov_np).double(), torch.from_numpy(fix_np).double(), (8, 4, 2, 1, 1), 6, 1.0)
+    s64 = orc.grad3d_loss(f64) + (f64 * r.double()).mean()
+    g64 = dict(zip(p64, torch.autograd.grad(s64, list(p64.values()))))
+    mov, fix = torch.from_numpy(mov_np).cuda(), torch.from_numpy(fix_np).cuda()
+    y, flow = m(mov, fix)
+    assert tuple(y.shape) == (1, 2) + shape
+    ef = assert_close(np64(flow), f64.detach().numpy(), atol=2e-3, rtol=0, what="flow (voxels)")
+    assert_close(np64(y), y64.detach().numpy(), atol=5e-4, rtol=0, what="y_moved")
+    s = losses.Grad3d(penalty="l2")(flow, fix) + (flow * r.cuda()).mean()
+    assert abs(float(s.detach()) - float(s64.detach())) < 2e-6
+    s.backward()
+    worst, at = _worst_grad(((n, p.grad) for n, p in m.named_parameters()), g64)
+    _note("config[in_channel_2].flow_maxerr_voxels", ef)
+    _note("config[in_channel_2].grad_worst_rel_to_max", worst)
+    assert worst < 5e-3, (worst, at)
+
+
+def test_operator_path_at_another_head_layout():
+    """ModeT_cu(fused_attention=False) at num_heads=[4,4,2,1,1]: the modetqkrpb_cu operator path matches the fused model and the
+    fp64 oracle (flow, loss, every gradient)"""
+    from oracle import modet_torch as orc
+    from smilecode_amd import losses, synth
+    shape, kw = (48, 64, 48), {"num_heads": [4, 4, 2, 1, 1]}
+    mov_np, fix_np = synth.make_pair(shape, 24)
+    mov, fix = torch.from_numpy(mov_np).cuda(), torch.from_numpy(fix_np).cuda()
+    res = {}
+    for fused in (True, False):
+        m, w = _cfg_model(shape, kw, "ModeT_cu", fused_attention=fused)
+        y, flow = m(mov, fix)
+        loss = losses.NCC_vxm()(fix, y) + losses.Grad3d(penalty="l2")(flow, fix)
+        loss.backward()
+        res[fused] = (flow.detach(), float(loss), [(n, p.grad.clone()) for n, p in m.named_parameters()])
+    ef = float((res[True][0] - res[False][0]).abs().max())
+    assert ef < 1e-3 and abs(res[True][1] - res[False][1]) < 2e-6, (ef, res[True][1], res[False][1])
+    p64 = {n: torch.from_numpy(v).double().requires_grad_(True) for n, v in w.items()}
+    l64, _, _, _, f64 = orc.train_loss(p64, torch.from_numpy(mov_np).double(), torch.from_numpy(fix_np).double(), [4, 4, 2, 1, 1], 6, 1.0)
+    g64 = dict(zip(p64, torch.autograd.grad(l64, list(p64.values()))))
+    eo = float((res[False][0].double().cpu() - f64.detach()).abs().max())
+    assert eo <= 2e-3 and abs(res[False][1] - float(l64)) < 2e-6, (eo, res[False][1], float(l64))
+    for fused in (True, False):
+        worst, at = _worst_grad(res[fused][2], g64)
+        _note(f"config[operator_heads_4_4_2,fused={int(fused)}].grad_worst_rel_to_max", worst)
+        assert worst < 5e-3, (fused, worst, at)
+    _note("config[operator_heads_4_4_2].flow_maxerr_vs_fp64", eo)
+    _note("config[operator_heads_4_4_2].flow_maxdiff_vs_fused", ef)
+
+
+def test_trainer_paths_at_another_head_layout():
+    """engine.Trainer on num_heads=[4,4,2,1,1], whose levels 4 and 5 take two UNPAIRED projection nodes sharing the parameters:
+    the first writes its gradients into the flat buffer (StepContext.claim), the second returns them to autograd, and
+    FlatParams.gather_grads / Trainer._staged_backward add those on top.  The flat gradient of the product step against the
+    fp64 oracle; eager steps, a hipGraph replay and deterministic mode bit-reproducible; the three-stage backward equal to
+    the plain one; one Adam step against the oracle's update on the same gradient."""
+    from oracle import modet_torch as orc
+    from smilecode_amd import ops, synth
+    from smilecode_amd.engine import Trainer
+    shape, kw = (32, 48, 32), {"num_heads": [4, 4, 2, 1, 1]}
+    mov, fix = _pair(shape)
+    a = Trainer(_cfg_model(shape, kw)[0])
+    names = [n for n, _ in a.model.named_parameters()]
+    assert not ops._L().modet_proj_ln_bwd_pair_ws_bytes(4096, 128, 24), "level 5 must take the unpaired projection nodes"
+    p64 = {n: torch.from_numpy(v).double().requires_grad_(True) for n, v in synth.make_weights(24, 4, 6, [4, 4, 2, 1, 1]).items()}
+    l64, _, _, _, _ = orc.train_loss(p64, mov.double().cpu(), fix.double().cpu(), [4, 4, 2, 1, 1], 6, 1.0)
+    g64 = dict(zip(p64, torch.autograd.grad(l64, list(p64.values()))))
+    la = a._fwd_bwd(mov, fix)
+    assert abs(float(la[0]) - float(l64)) < 2e-6
+    g1 = a.fp.grad.clone()
+    worst, at = _worst_grad(((n, g1[off:off + k]) for n, (off, k) in zip(names, a.fp.offsets)), {n: g64[n].reshape(-1) for n in names})
+    _note("trainer_heads_4_4_2.flat_grad_worst_rel_to_max", worst)
+    assert worst < 5e-3, (worst, at)
+    a._fwd_bwd(mov, fix)
+    assert torch.equal(a.fp.grad, g1), "two eager steps differ"
+    b = Trainer(_cfg_model(shape, kw)[0]).capture(mov, fix)
+    for _ in range(2):
+        b.fp.grad.fill_(float("nan"))
+        b._graph.replay()
+        assert torch.equal(b.fp.grad, g1), "a hipGraph replay differs from the eager step"
+    c = Trainer(_cfg_model(shape, kw)[0], overlap_allreduce=True)
+    c._fwd_bwd_staged(mov, fix)
+    assert torch.equal(c.fp.grad, g1), float((c.fp.grad - g1).abs().max() / g1.abs().max())
+    prev = ops.set_deterministic(True)
+    try:
+        d = Trainer(_cfg_model(shape, kw)[0])
+        d._fwd_bwd(mov, fix)
+        gd = d.fp.grad.clone()
+        d._fwd_bwd(mov, fix)
+        assert torch.equal(d.fp.grad, gd), "deterministic mode: two steps differ"
+        assert float((gd - g1).abs().max() / g1.abs().max()) <= 1e-5
+    finally:
+        ops.set_deterministic(prev)
+    e = Trainer(_cfg_model(shape, kw)[0])
+    flat0 = e.fp.flat.double().cpu()
+    e.train_step(mov, fix, epoch=0)
+    grad = e.fp.grad.double().cpu()
+    par = {"all": flat0.clone()}
+    orc.adam_amsgrad_step(par, {"all": grad}, {"all": tuple(torch.zeros_like(flat0) for _ in range(3))}, e.lr_last, 1)
+    aerr = float((e.fp.flat.double().cpu() - par["all"]).abs().max())
+    _note("trainer_heads_4_4_2.adam_step_maxerr", aerr)
+    # (the update moves parameters by ~lr = 1e-4; the fp32 parameters round at <= 1.2e-7 for |p| < 2)
+    assert float((e.fp.flat.double().cpu() - flat0).abs().max()) > 5e-5 and aerr < 2.5e-7, aerr
+
+
 def test_full_size_properties():
     """BASELINE size 160x192x160: size-independent properties of the forward."""
     shape = (160, 192, 160)

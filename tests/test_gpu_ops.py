@@ -579,8 +579,13 @@ def test_projection_golden(ops, tag):
         assert_close(np64(got), g[f"{tag}.{n}"], atol=2e-4, rtol=1e-4, what=f"proj {n}")
 
 
+# generic (Cin, dim) pairs of other head layouts (no grouped kernel) at their level's voxel count of 160x192x160:
+# level 5 = 1200, level 4 = 9600, level 3 = 76800
+GENERIC_PROJ = [(128, 12, 1200), (128, 24, 1200), (64, 12, 9600), (64, 48, 9600), (32, 24, 9600), (32, 48, 76800)]
+
+
 @pytest.mark.parametrize("cin,dim,n", [(8, 6, 70001), (16, 6, 5003), (32, 12, 9001), (64, 24, 1531), (128, 48, 1203),
-                                       (128, 48, 7), (24, 12, 777)])
+                                       (128, 48, 7), (24, 12, 777)] + GENERIC_PROJ)
 def test_projection_vs_oracle_large(ops, orc, cin, dim, n):
     gen = torch.Generator().manual_seed(11)
     x = torch.randn((1, cin, 1, 1, n), generator=gen).double().requires_grad_(True)
@@ -604,7 +609,7 @@ def test_projection_vs_oracle_large(ops, orc, cin, dim, n):
 
 
 @pytest.mark.parametrize("cin,dim,n", [(8, 6, 70001), (16, 6, 5003), (32, 12, 9001), (64, 24, 1531), (128, 48, 1203),
-                                       (24, 12, 777)])
+                                       (24, 12, 777)] + GENERIC_PROJ)
 def test_projection_pair_vs_oracle(ops, orc, cin, dim, n):
     """ops.proj_ln_pair (the layer applied to the fixed and the moving features of a level): outputs and data gradients as
     two single applications, parameter gradients of both uses summed in one reduction -- against the fp64 oracle of
@@ -1384,6 +1389,66 @@ def test_cwm_golden(tag, heads):
     assert_close(ncdhw(grads[0]), g[f"{tag}.dx"], atol=5e-5, what="cwm dx")
     for n, gq in zip(names, grads[1:]):
         assert_close(np64(gq), g[f"{tag}.g.{n}"], atol=2e-4, rtol=2e-4, what=f"cwm d{n}")
+
+
+@pytest.mark.parametrize("heads,shape,B", [(4, (10, 12, 10), 1), (8, (10, 12, 10), 1), (4, (20, 24, 20), 1), (8, (20, 24, 20), 1),
+                                           (4, (40, 48, 40), 1), (4, (10, 12, 14), 2), (8, (10, 12, 14), 2),
+                                           (4, (20, 24, 28), 2), (8, (20, 24, 28), 2)])
+def test_cwm_at_full_size_levels_vs_oracle(ops, orc, heads, shape, B):
+    """the CWM module (upsample, ConvIns 3h -> 6h, ConvIns 6h -> 6h, conv 6h -> h, softmax-weighted sum of the h fields) with 4
+    and 8 heads at the level-5 / 4 / 3 inputs of 160x192x160 and, with B = 2, of 160x192x224 -- what head layouts other than
+    the default run (the default model has 8 heads at level 5 only): forward and every gradient against the fp64 oracle.
+    The conv kernel family of each launch is asserted (csrc/conv3d_q.hip forward / data gradient, csrc/conv3d_wtr.hip weight
+    gradient).  (8 heads at the level-3 input of 160x192x160 run the same families; its fp64 oracle takes ~15 s of host time.)"""
+    from smilecode_amd.models import CWM
+    L = ops._L()
+    c = 3 * heads
+    up = tuple(2 * s for s in shape)
+    for cin, cout, variant in ((c, 2 * c, 3), (2 * c, 2 * c, 2), (2 * c, heads, 2)):
+        fams = tuple(L.modet_conv3d_kernel_family_v(B, *up, cin, cout, p, variant) for p in (0, 1, 2))
+        assert fams == (5, 5, 4), f"CWM conv {cin} -> {cout} at {up}, B={B}: families (fwd, dgrad, wgrad) {fams}"
+    gen = torch.Generator().manual_seed(heads * 1000 + shape[2] + B)
+    mod = CWM(c, 2 * c)
+    p = {}
+    with torch.no_grad():
+        for n, q in mod.named_parameters():
+            fan = q.shape[1] * 27 if q.dim() == 5 else mod.conv[2].weight.shape[1] * 27
+            q.copy_((torch.rand(q.shape, generator=gen) * 2 - 1) / np.sqrt(fan))
+            p["m." + n] = q.detach().double().clone().requires_grad_(True)
+    mod = mod.cuda()
+    # the CWM's input is an attention output: expected offsets, |x| <= 1 (the module's first conv relies on it, models.CWM)
+    x = (torch.rand((B, c) + shape, generator=gen) * 2 - 1).double().requires_grad_(True)
+    ref = orc.cwm(p, "m", x, heads)
+    gy = torch.randn(ref.shape, generator=gen).double()
+    rg = torch.autograd.grad(ref, [x] + list(p.values()), gy)
+    xd = cl(x.detach().numpy()).requires_grad_(True)
+    y = mod(xd)
+    gd = torch.autograd.grad(y, [xd] + list(mod.parameters()), cl(gy.numpy()))
+    tag = f"cwm_h{heads}_{'x'.join(map(str, shape))}_B{B}"
+
+    def rel(a, b):
+        return float(np.abs(a - b).max() / np.abs(b).max())
+
+    e = rel(ncdhw(y), ref.detach().numpy())
+    _note(f"{tag}.out_relerr", e)
+    assert e <= 1e-5, e
+    # LeakyReLU's kink: a normalised element within fp32 noise of 0 (these inputs have them at 2e-8 .. 7e-7) may take the other
+    # slope on the GPU and move d_x by a few 1e-3 of its max locally, and through the InstanceNorm backward's means by ~1e-5 of
+    # it everywhere in its channel (as in test_instnorm_conv_chain_with_fused_backward_statistics): compare in the mean and bound
+    # the outliers.  Without a flip the error is ~5e-7 of the max.
+    ex, dmax = np.abs(ncdhw(gd[0]) - rg[0].numpy()), float(rg[0].abs().max())
+    _note(f"{tag}.dx_relerr", float(ex.max()) / dmax)
+    _note(f"{tag}.dx_mean_relerr", float(ex.mean()) / dmax)
+    assert float(ex.mean()) <= 1e-4 * dmax and float(ex.max()) <= 5e-2 * dmax, (float(ex.mean()) / dmax, float(ex.max()) / dmax)
+    worst = 0.0
+    for (n, _), a, b in zip(mod.named_parameters(), gd[1:], rg[1:]):
+        if n.endswith("main.bias"):
+            continue                      # (a conv bias in front of an InstanceNorm: analytically zero)
+        worst = max(worst, rel(np64(a), b.numpy()))
+    _note(f"{tag}.param_grad_relerr", worst)
+    # (a kink flip also moves the weight gradients of the layers upstream of it: by 7e-3 of the max at 10x12x10, one flip among
+    # 9 600 voxels; without one they agree to ~1e-6)
+    assert worst <= 2e-2, worst
 
 
 # ------------------------------------------------------------------------------------------------ losses
