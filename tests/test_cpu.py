@@ -867,3 +867,26 @@ def test_gradient_maximum_tag_dies_with_in_place_accumulation():
     assert ops._amax_of(t) is not None
     t.add_(1)
     assert ops._amax_of(t) is None
+
+
+def test_gradient_yardstick_scores_each_tensor_against_aten_fp32():
+    """tests/util.grad_yardstick on the oracle's own fp64 / fp32 gradients at 16x32x16: the fp32 set passes as the candidate,
+    the analytically-zero conv biases are not scored, and a candidate with ONE tensor scaled by 1 + 1e-3 (the size of error a
+    kernel can add while every gradient stays inside the old flat 5e-3 bound) fails at A = GRAD_A, the message naming that
+    tensor and its two errors.  (The GPU test at this shape holds some tensors to a pinned A of their own: GRAD_A_OPEN.)"""
+    from tests.util import GRAD_A, GRAD_FLOOR, grad_yardstick, oracle_train_grads
+    from smilecode_amd import synth
+    w = synth.make_weights(24)
+    mov, fix = synth.make_pair((16, 32, 16), 31)
+    g64 = oracle_train_grads(w, mov, fix)[-1]
+    g32 = oracle_train_grads(w, mov, fix, dtype=torch.float32)[-1]
+    res = grad_yardstick("selftest[16x32x16]", g64, g32, g32, record=False)
+    zero = {n for n, g in g64.items() if float(g.abs().max()) < 1e-8}
+    assert zero and all(n.endswith("main.bias") for n in zero) and set(res) == set(g64) - zero
+    assert all(h == f and 0 < f < 1e-3 for h, f in res.values())
+    name = "encoder.conv1.1.main.weight"
+    off = dict(g32, **{name: g32[name] * (1 + 1e-3)})
+    assert float((off[name] - g64[name]).abs().max()) < 5e-3 * float(g64[name].abs().max())
+    with pytest.raises(AssertionError, match=name.replace(".", r"\.") + r": e_hip 1\.\d+e-03, e_f32 "):
+        grad_yardstick("selftest[16x32x16]", g64, g32, off, record=False)
+    assert GRAD_A * res[name][1] + GRAD_FLOOR < 1e-3

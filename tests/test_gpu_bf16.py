@@ -315,7 +315,7 @@ def test_cfg5_shape_fp32_parity_vs_fp64_oracle(cfg5_oracle):
     parameter gradient <= 5e-3 of its tensor's max on sample 0 (the oracle's autograd ran there) -- and the batch-2
     gradient is the mean of the two single-sample gradients (the loss is a mean over the batch; that linearity pins the
     batch-2 step the bench times without a second fp64 tape)."""
-    from tests.util import note
+    from tests.util import grad_yardstick, note, note_many
     o = cfg5_oracle
     m = _cfg5_model(torch.float32, o["w"])
     mov, fix = torch.from_numpy(o["mov"]).cuda(), torch.from_numpy(o["fix"]).cuda()
@@ -331,7 +331,10 @@ def test_cfg5_shape_fp32_parity_vs_fp64_oracle(cfg5_oracle):
         if err / gmax > worst:
             worst, worst_name = err / gmax, n
     note("cfg5_f32[160x192x224].grad_worst_rel_to_max", worst)
+    note("oracle_job[cfg5].wall_s", o["job_wall_s"])
+    note("oracle_job[cfg5].peak_rss_gb", o["job_peak_rss_gb"])
     assert worst <= 5e-3, f"worst gradient error {worst:.3e} of max|g| in {worst_name}"        # (measured 6.3e-4)
+    grad_yardstick("cfg5_f32[160x192x224]", o["grad0"], o["grad0_32"], g0)
     s1, r1, fl1, g1 = _loss_and_grads(m, mov[1:], fix[1:])
     sb, rb, flb, gb = _loss_and_grads(m, mov, fix)
     e = float((flb.double().cpu() - o["flow"]).abs().max())
@@ -343,19 +346,23 @@ def test_cfg5_shape_fp32_parity_vs_fp64_oracle(cfg5_oracle):
     note("cfg5_f32[160x192x224,B=2].flow_maxdiff_batch2_vs_single", indep)
     assert indep < 1e-3, indep
     assert abs(sb - 0.5 * (s0 + s1)) < 5e-6 and abs(rb - 0.5 * (r0 + r1)) < 5e-7
-    lin = 0.0
+    lin, lin_at, per = 0.0, "", {}
     for n in gb:
         if float(o["grad0"][n].abs().max()) < 1e-8:         # conv bias under InstanceNorm: analytically zero, fp32 noise
             continue
         want = 0.5 * (g0[n] + g1[n])
         gmax = float(want.abs().max())
-        lin = max(lin, float((gb[n] - want).abs().max()) / gmax)
+        per[f"cfg5_f32[160x192x224,B=2].grad_batch_linearity_relerr.{n}"] = e = float((gb[n] - want).abs().max()) / gmax
+        if e > lin:
+            lin, lin_at = e, n
+    note_many(per)
     note("cfg5_f32[160x192x224,B=2].grad_batch_linearity_relerr", lin)
-    # fp32 summation order + the warp scatter's atomics + (round 3) the coarse-level forward convs: a self-consistency check
-    # between fp32 runs, each within 2e-2 of the oracle.  Measured per parameter (tools/exp_linearity.py,
-    # profiles/r03s_direct_conv_accuracy.txt): <= 3.4e-4 everywhere except the two CWM5 weights behind two InstanceNorms of
-    # nearly constant maps, 8e-4 / 2.6e-3 with conv_direct_kernel (7.7e-4 worst with the tiled kernel, which is 2x LESS accurate)
-    assert lin < 5e-3, lin
+    # a self-consistency check between three fp32 runs of HIP (batch 2 against the mean of the two single-sample runs), per
+    # tensor in the parity report; the batch-2 step itself is held to the fp64 oracle with the yardstick in
+    # test_forward_vs_oracle_64_batch2 (test_gpu_e2e.py), sample 0 above.  Measured 4.76e-3, on encoder.conv2.2.main.weight
+    # (then conv3.2 / conv4.2, cwm5.conv.1, projblock5: 3.7e-3 .. 4.2e-3), a tensor on which sample 0's HIP gradient is 4.7e-4
+    # off the fp64 oracle, closer than ATen fp32's 7.0e-4
+    assert lin < 5e-3, (lin, lin_at)
 
 
 def test_cfg5_shape_bf16_flow_and_dice_vs_fp64_oracle(cfg5_oracle):
