@@ -594,14 +594,7 @@ int tiles_launch(const void* src, int src_bf16, const float* flow, const float* 
   if (src_bf16) { if (small) WT_FILL(true, 1); else WT_FILL(true, 4); }
   else { if (small) WT_FILL(false, 1); else WT_FILL(false, 4); }
 #undef WT_FILL
-  int half = 0;
-#ifdef MODET_TUNING
-  if (const char* e = getenv("WT_NCH4")) half = atoi(e);
-#endif
-  if (half == 1) hipLaunchKernelGGL((accumulate_kernel<4, 256>), dim3(nt, C / 4), dim3(256), 0, s, L, (const unsigned*)w.amax, d_src, w.border, g);
-  else if (half == 2) hipLaunchKernelGGL((accumulate_kernel<4, 512>), dim3(nt, C / 4), dim3(512), 0, s, L, (const unsigned*)w.amax, d_src, w.border, g);
-  else if (half == 3) hipLaunchKernelGGL((accumulate_kernel<8, 256>), dim3(nt, C / 8), dim3(256), 0, s, L, (const unsigned*)w.amax, d_src, w.border, g);
-  else hipLaunchKernelGGL((accumulate_kernel<8, ACC>), dim3(nt, C / 8), dim3(ACC), 0, s, L, (const unsigned*)w.amax, d_src, w.border, g);
+  hipLaunchKernelGGL((accumulate_kernel<8, ACC>), dim3(nt, C / 8), dim3(ACC), 0, s, L, (const unsigned*)w.amax, d_src, w.border, g);
   hipLaunchKernelGGL(border_kernel<false>, dim3(nt, C / 8), dim3(256), 0, s, d_src, (const float*)w.border, (const unsigned*)w.cursor, g);
   return modet_launch_status();
 }

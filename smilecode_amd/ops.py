@@ -192,14 +192,6 @@ def _conv16_tag(kind, x_shape, Cin, Cout, x_bf16):
 
 
 # ------------------------------------------------------------------------------------------------ raw calls
-# The one un-normalised activation of the model is the ConvBlock 1 -> 4 output in front of the first ConvInsBlock (reference
-# models.py:192).  Default (False): that 4 -> 8 layer runs the three bf16 pieces -- range-free, and the most accurate form: flow
-# error vs fp64 at 160x192x160 4.3e-4 voxels, worst gradient 6.4e-4 of its tensor's max.  True: the first block's kernel leaves
-# max |y| on the device and the 4 -> 8 layer (forward + weight gradient) scales two f16 pieces by it -- also range-free, 0.05 ms
-# per step faster (6.94 vs 6.99), but 7.2e-4 / 4.4e-3 (measured, profiles/r06*_first_block_f16.txt): not worth the margin.
-FIRST_BLOCK_F16 = False
-
-
 def conv3d_forward(x, w, b, act, step=None, x_act=False):
     """x_act: the caller's word that x is an activation inside the f16 forms' range (include/modet_hip.h, "TWO f16 PIECES":
     |x| < 4 094) -> the *_bounded entry point, half the matrix work; without it the launch makes no assumption about x (three
@@ -216,14 +208,6 @@ def conv3d_forward(x, w, b, act, step=None, x_act=False):
     ws = _ws(nb, x)
     n = float(B) * D * H * W
     with _Guard(x, _conv_tag("fwd", x.shape, Cin, Cout, 1 if act else 0, f16=bool(x_act)), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
-        if FIRST_BLOCK_F16 and Cin == 1 and Cout == 4 and B * D * H * W >= 500000 and not x_act:
-            # the first encoder block: its kernel leaves max |y| on the device for free, and the next layer (whose input this
-            # un-normalised tensor is) scales its f16 pieces by it -- any image range at the f16 forms' speed
-            amax = torch.empty(AMAX_FLOATS, dtype=torch.float32, device=x.device)
-            rc = L.modet_conv3d_fwd_amax_out(_p(x), _p(w), _p(b), _p(y), _p(ws), nb, B, D, H, W, Cin, Cout, int(act), _p(amax),
-                                             _stream(), _h(step))
-            if rc == 0:
-                return _tag_xamax(y, amax)
         fn = L.modet_conv3d_fwd_bounded if x_act else L.modet_conv3d_fwd
         _lib.check(fn(_p(x), _p(w), _p(b), _p(y), _p(ws), nb, B, D, H, W, Cin, Cout, int(act), _stream(), _h(step)), "modet_conv3d_fwd")
     return y
@@ -308,17 +292,6 @@ def _tag_amax(t, amax):
     return t
 
 
-def _tag_xamax(t, amax):
-    """mark an ACTIVATION tensor with the device-side maxima of its magnitude (left by the kernel that produced it)"""
-    t._modet_xamax = (amax, t._version)
-    return t
-
-
-def _xamax_of(t):
-    tag = getattr(t, "_modet_xamax", None)
-    return tag[0] if tag is not None and tag[1] == t._version else None
-
-
 def _amax_of(t):
     tag = getattr(t, "_modet_amax", None)
     if tag is None or not GRAD_F16 or tag[1] != t._version:
@@ -370,8 +343,6 @@ class StepContext:
         self.written = set()
         self._keep = []
         self._leaf = []              # queued leaf reductions (modet_leaf_job_t) of the open deferred() scope, see defer_leaf
-        self._side = {}              # device index -> the stream the small levels' weight gradients run on (see side_stream)
-        self._side_used = None
 
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
@@ -434,9 +405,6 @@ class StepContext:
             sc = self.sc
             super().__exit__(*exc)
             sc.dst = None
-            if sc._side_used is not None:                # the partial tiles the side stream produced: join before reducing them
-                torch.cuda.current_stream().wait_stream(sc._side_used)
-                sc._side_used = None
             rc = _L().modet_conv3d_wgrad_defer_flush(sc.handle, _stream())    # always empties the queue, also on an exception
             jobs, sc._leaf = sc._leaf, []
             if exc[0] is None and jobs:                  # the attention / projection parameter gradients of every level: one launch
@@ -457,21 +425,6 @@ class StepContext:
         pointers written are in ``scope.written``.  A conv without a destination, or a second use of the same weight inside
         one scope, takes the immediate path."""
         return StepContext._Deferred(self, dst)
-
-    def side_stream(self, like):
-        """Fork: the stream the weight gradients of the SMALL levels run on, made to wait for everything enqueued on the
-        current stream so far (their operands).  Pyramid levels 3-5 and the CWM layers are latency-bound launches of 100-1000
-        workgroups on 256 CUs; the data gradient is what the next layer waits for, the weight gradient is needed only at the end
-        of the pass (the deferred reduction), so the two chains run side by side -- as two branches of the captured hipGraph.
-        The scope's flush joins.  Callers keep the operands alive until then (``_keep``): a tensor freed on the main stream
-        could otherwise be handed out again while the side stream still reads it."""
-        dev = like.device.index if like.device.index is not None else torch.cuda.current_device()
-        side = self._side.get(dev)
-        if side is None:
-            side = self._side[dev] = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        self._side_used = side
-        return side
 
     def destinations(self, w, b, want_bias):
         """(d_w, d_bias) destinations for this call, or None -> immediate path"""
@@ -549,79 +502,55 @@ def _h(step):
     return None if step is None else step.handle
 
 
-# Weight gradients of launches with at most this many voxels (batch included) run on the step context's side stream, beside
-# the data-gradient chain (StepContext.side_stream); 0 = everything on one stream (the default).  Measured in round 5
-# (profiles/r05s_ab_side_wgrad.txt, 160x192x160, one box, alternating): 0 -> 8.29 / 8.35 ms, 700 000 (levels 3-5 + CWM) ->
-# 8.65 / 8.32, 1 300 000 -> 8.34, everything -> 8.34: no gain -- every fork is an extra cross-stream edge of the hipGraph (the
-# host cost of a replay goes from 0.27 to 1.03 ms) and the 17 forks cost what the overlap of those 20-50 us kernels buys.
-SIDE_WGRAD_MAX_VOXELS = float(os.environ.get("MODET_SIDE_WGRAD_MAX_VOXELS", "0"))
-
-
-def conv3d_backward_weight(x, dy, want_bias, y_act=None, w=None, b=None, step=None, amax=None, norm=None, x_amax=None):
+def conv3d_backward_weight(x, dy, want_bias, y_act=None, w=None, b=None, step=None, amax=None, norm=None):
     """d_w, d_bias; with y_act (ConvBlock 1 -> 4 only) dy is the gradient w.r.t. LeakyReLU(conv) and the activation's
     derivative is applied while loading it.  With a StepContext (given, or bound to this thread) whose ``deferred()`` scope
     knows destinations for the parameters ``w`` / ``b``, the gradients go straight there at the scope's flush and
     (None, None) is returned.  amax: one-float tensor >= max |dy| (see _tag_amax) and the caller's word that x is an
     activation: the z-marching kernel then runs on two f16 pieces.  norm = (mean, rstd): x is a RAW ConvInsBlock output,
-    normalised while the kernel stages it (modet_conv3d_bwd_weight_normin; only where modet_conv3d_bwd_weight_normin_ok).
-    x_amax: the maxima of |x| on the device (see _tag_xamax) for an x that is NOT an activation: scaled by them instead."""
+    normalised while the kernel stages it (only where the library's *_normin_ok says so)."""
     _chk(x, dy)
     B, D, H, W, Cin = x.shape
     Cout = dy.shape[-1]
     L = _L()
     nb = L.modet_conv3d_bwd_weight_ws_bytes(B, D, H, W, Cin, Cout)
     n = float(B) * D * H * W
+    f16 = amax is not None and y_act is None
+
+    def launch(dw, db, ws, scope):
+        """the one library call: ``scope`` = the StepContext whose flush reduces the partial tiles, None = they are reduced now"""
+        if norm is not None:
+            fn, head, tail = L.modet_conv3d_bwd_weight_normin, (x, norm[0], norm[1], dy), (_p(amax), _stream(), _h(scope))
+        elif f16:
+            fn, head, tail = L.modet_conv3d_bwd_weight_amax, (x, dy), (_p(amax), _stream(), _h(scope))
+        elif scope is not None:
+            fn, head, tail = L.modet_conv3d_bwd_weight_defer, (x, dy, y_act), (_stream(), _h(scope))
+        elif y_act is not None:
+            fn, head, tail = L.modet_conv3d_bwd_weight_act, (x, dy, y_act), (_stream(),)
+        else:
+            fn, head, tail = L.modet_conv3d_bwd_weight, (x, dy), (_stream(),)
+        with _Guard(x, _conv_tag("wgrad", x.shape, Cin, Cout, f16=f16), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
+            _lib.check(fn(*map(_p, head), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin, Cout, *tail), fn.__name__)
+
     scope = step if step is not None else current_step()
     dst = scope.destinations(w, b, want_bias) if scope is not None else None
-    if dst is not None:
-        dw, db = dst
-        if SIDE_WGRAD_MAX_VOXELS and n <= SIDE_WGRAD_MAX_VOXELS and _TIMER is None:
-            with torch.cuda.stream(scope.side_stream(x)):
-                ws = _ws(nb, x)
-                _lib.check(L.modet_conv3d_bwd_weight_defer(_p(x), _p(dy), _p(y_act), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin,
-                                                           Cout, _stream(), _h(scope)), "modet_conv3d_bwd_weight_defer")
-            scope._keep.extend((x, dy, y_act))                # read by the side stream: alive until the flush joins it
-        else:
-            ws = _ws(nb, x)
-            with _Guard(x, _conv_tag("wgrad", x.shape, Cin, Cout, f16=amax is not None and y_act is None), 54.0 * Cin * Cout * n,
-                        4.0 * n * (Cin + Cout)):
-                if norm is not None:
-                    _lib.check(L.modet_conv3d_bwd_weight_normin(_p(x), _p(norm[0]), _p(norm[1]), _p(dy), _p(dw), _p(db), _p(ws), nb,
-                                                                B, D, H, W, Cin, Cout, _p(amax), _stream(), _h(scope)),
-                               "modet_conv3d_bwd_weight_normin")
-                elif amax is not None and y_act is None:
-                    _lib.check(L.modet_conv3d_bwd_weight_amax2(_p(x), _p(dy), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin, Cout,
-                                                               _p(amax), _p(x_amax), _stream(), _h(scope)), "modet_conv3d_bwd_weight_amax")
-                else:
-                    _lib.check(L.modet_conv3d_bwd_weight_defer(_p(x), _p(dy), _p(y_act), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin,
-                                                               Cout, _stream(), _h(scope)), "modet_conv3d_bwd_weight_defer")
-        scope._keep.append(ws)                                # the partial tiles must survive until the flush
-        if amax is not None:
-            scope._keep.extend((amax, x_amax))                # (a queued launch reads the maxima at the flush, too)
-        if y_act is None and L.modet_conv3d_wgrad_defers_operands(B, D, H, W, Cin, Cout):
-            scope._keep.extend((x, dy))                       # small levels: the launch itself is queued and reads them at the flush
-        scope.written.add(w.data_ptr())
-        if db is not None:
-            scope.written.add(b.data_ptr())
-        return None, None
     ws = _ws(nb, x)
-    dw = torch.empty((Cout, Cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
-    with _Guard(x, _conv_tag("wgrad", x.shape, Cin, Cout, f16=amax is not None and y_act is None), 54.0 * Cin * Cout * n,
-                4.0 * n * (Cin + Cout)):
-        if norm is not None:
-            _lib.check(L.modet_conv3d_bwd_weight_normin(_p(x), _p(norm[0]), _p(norm[1]), _p(dy), _p(dw), _p(db), _p(ws), nb, B, D, H,
-                                                        W, Cin, Cout, _p(amax), _stream(), None), "modet_conv3d_bwd_weight_normin")
-        elif y_act is not None:
-            _lib.check(L.modet_conv3d_bwd_weight_act(_p(x), _p(dy), _p(y_act), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin,
-                                                     Cout, _stream()), "modet_conv3d_bwd_weight_act")
-        elif amax is not None:
-            _lib.check(L.modet_conv3d_bwd_weight_amax2(_p(x), _p(dy), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin, Cout, _p(amax),
-                                                       _p(x_amax), _stream(), None), "modet_conv3d_bwd_weight_amax")
-        else:
-            _lib.check(L.modet_conv3d_bwd_weight(_p(x), _p(dy), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin, Cout,
-                                                 _stream()), "modet_conv3d_bwd_weight")
-    return dw, db
+    if dst is None:
+        dw = torch.empty((Cout, Cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+        db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
+        launch(dw, db, ws, None)
+        return dw, db
+    dw, db = dst
+    launch(dw, db, ws, scope)
+    scope._keep.append(ws)                                # the partial tiles must survive until the flush
+    if amax is not None:
+        scope._keep.append(amax)                          # (a queued launch reads the maximum at the flush, too)
+    if y_act is None and L.modet_conv3d_wgrad_defers_operands(B, D, H, W, Cin, Cout):
+        scope._keep.extend((x, dy))                       # small levels: the launch itself is queued and reads them at the flush
+    scope.written.add(w.data_ptr())
+    if db is not None:
+        scope.written.add(b.data_ptr())
+    return None, None
 
 
 # ------------------------------------------------------------------------------------------------ autograd ops
@@ -648,7 +577,6 @@ class _Conv3d(Function):
             with _Guard(dy, "lrelu_bwd", dy.numel(), 12.0 * dy.numel()):
                 _lib.check(_L().modet_lrelu_bwd(_p(dy), _p(y), _p(g), dy.numel(), _stream()), "modet_lrelu_bwd")
             dy = g
-        # (the weight gradient first: on the small levels it goes to the side stream and runs beside the data gradient)
         amax = None if ctx.act else _amax_of(dy)                 # (x is whatever the caller convolved: no f16 weight gradient)
         dw, db = conv3d_backward_weight(x, dy, ctx.has_bias, w=w, b=b, step=ctx.step)
         dx = conv3d_backward_data(dy, w, x.shape[-1], ctx.step, amax) if ctx.needs_input_grad[0] else None
@@ -672,18 +600,10 @@ class _Conv3dStats(Function):
         sb = L.modet_conv3d_stats_bytes(B, D, H, W, Cin, Cout)
         stats = torch.empty(sb // 4, dtype=torch.float32, device=x.device)
         n = float(B) * D * H * W
-        # x is not an activation but its producer left max |x| on the device (the ConvBlock 1 -> 4 output, _tag_xamax): the f16
-        # pieces are scaled by it (z-marching family; the others ignore it and run bf16x3)
-        ctx.x_amax = None if ctx.x_act else _xamax_of(x)
-        f16 = ctx.x_act or (ctx.x_amax is not None and L.modet_conv3d_kernel_family_v(B, D, H, W, Cin, Cout, 0, 3) == 2)
-        with _Guard(x, _conv_tag("fwd", x.shape, Cin, Cout, 3, f16=f16), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
-            if ctx.x_amax is not None:
-                _lib.check(L.modet_conv3d_fwd_stats_amax(_p(x), _p(w), _p(b), _p(y), _p(ws), nb, _p(stats), sb, B, D, H, W, Cin, Cout,
-                                                         _p(ctx.x_amax), _stream(), _h(ctx.step)), "modet_conv3d_fwd_stats_amax")
-            else:
-                fn = L.modet_conv3d_fwd_stats_bounded if ctx.x_act else L.modet_conv3d_fwd_stats
-                _lib.check(fn(_p(x), _p(w), _p(b), _p(y), _p(ws), nb, _p(stats), sb, B, D, H, W, Cin, Cout, _stream(), _h(ctx.step)),
-                           "modet_conv3d_fwd_stats")
+        with _Guard(x, _conv_tag("fwd", x.shape, Cin, Cout, 3, f16=ctx.x_act), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
+            fn = L.modet_conv3d_fwd_stats_bounded if ctx.x_act else L.modet_conv3d_fwd_stats
+            _lib.check(fn(_p(x), _p(w), _p(b), _p(y), _p(ws), nb, _p(stats), sb, B, D, H, W, Cin, Cout, _stream(), _h(ctx.step)),
+                       "modet_conv3d_fwd_stats")
         ctx.has_bias = b is not None
         ctx.save_for_backward(x, w, b)
         ctx.mark_non_differentiable(stats)
@@ -697,8 +617,7 @@ class _Conv3dStats(Function):
         x, w, b = ctx.saved_tensors
         dy = dy.contiguous()
         amax = _amax_of(dy)
-        dw, db = conv3d_backward_weight(x, dy, ctx.has_bias, w=w, b=b, step=ctx.step,
-                                        amax=amax if (ctx.x_act or ctx.x_amax is not None) else None, x_amax=ctx.x_amax)
+        dw, db = conv3d_backward_weight(x, dy, ctx.has_bias, w=w, b=b, step=ctx.step, amax=amax if ctx.x_act else None)
         dx = conv3d_backward_data(dy, w, x.shape[-1], ctx.step, amax) if ctx.needs_input_grad[0] else None
         return dx, dw, db, None
 
@@ -831,7 +750,7 @@ class _InstNormConv(Function):
             dw, db = conv3d_backward_weight(y, dz, ctx.has_bias, w=w, b=b, step=ctx.step, amax=amax)   # (first: see _Conv3d.backward)
         if ctx.needs_input_grad[0]:
             d_raw = torch.empty_like(x_raw)
-            amax_out = _new_amax(x_raw)
+            amax_raw = _new_amax(x_raw)
             rb = L.modet_conv3d_bwd_data_instats_bytes(B, D, H, W, C, Cout) if FUSE_IN_DGRAD else 0
             if rb > 0:
                 d_y = torch.empty_like(x_raw)
@@ -847,7 +766,7 @@ class _InstNormConv(Function):
                 ws2 = _ws(nb2, x_raw)
                 with _Guard(x_raw, "instnorm_lrelu_bwd", 7.0 * x_raw.numel(), 12.0 * x_raw.numel()):
                     _lib.check(L.modet_instnorm_lrelu_bwd_rows_amax(_p(d_y), _p(x_raw), _p(mean), _p(rstd), _p(d_raw), _p(rows), rb,
-                                                                    _p(ws2), nb2, B, V, C, _p(amax_out), _stream()),
+                                                                    _p(ws2), nb2, B, V, C, _p(amax_raw), _stream()),
                                "modet_instnorm_lrelu_bwd_rows")
             else:
                 d_y = conv3d_backward_data(dz, w, C, ctx.step, amax)
@@ -855,8 +774,8 @@ class _InstNormConv(Function):
                 ws = _ws(nb, x_raw)
                 with _Guard(x_raw, "instnorm_lrelu_bwd", 14.0 * x_raw.numel(), 12.0 * x_raw.numel()):
                     _lib.check(L.modet_instnorm_lrelu_bwd_amax(_p(d_y), _p(x_raw), _p(mean), _p(rstd), _p(d_raw), _p(ws), nb, B, V, C,
-                                                               _p(amax_out), _stream()), "modet_instnorm_lrelu_bwd")
-            _tag_amax(d_raw, amax_out)
+                                                               _p(amax_raw), _stream()), "modet_instnorm_lrelu_bwd")
+            _tag_amax(d_raw, amax_raw)
         return d_raw, None, dw, db, None, None
 
 
@@ -1449,9 +1368,8 @@ def set_deterministic(on=True):
 # global memory.  Round 5 built it (off: break-even in the step); round 6 rebuilt it (payload lists, zero-d_out entries dropped
 # while binning, d_flow in the fill pass) and made it the default: faster AND bit-reproducible, so the plain step has no float
 # atomics left and set_deterministic() costs nothing for these warps.  WARP_TILES = False brings the float-atomic kernel back
-# (tools/ A/B runs).  Volumes below WARP_TILE_MIN_VOXELS keep it either way.
+# (tools/ A/B runs).
 WARP_TILES = True
-WARP_TILE_MIN_VOXELS = 0
 
 
 def _warp_bwd_tag(src, dsrc, add_flow, flow_bound):
@@ -1463,7 +1381,7 @@ def _warp_bwd_tag(src, dsrc, add_flow, flow_bound):
     if C == 3 and flow_bound:
         return "warp_bwd_gather3[C3]"
     s16 = src.dtype == torch.bfloat16
-    if (WARP_TILES and dsrc is not None and (C == 3 or not add_flow) and not (C == 3 and s16) and B * D * H * W >= WARP_TILE_MIN_VOXELS
+    if (WARP_TILES and dsrc is not None and (C == 3 or not add_flow) and not (C == 3 and s16)
             and _L().modet_warp_bwd_dsrc_tiles_ws_bytes(B, D, H, W, C)):
         return f"warp_bwd_tiles[C{C}]"
     return f"warp_bwd[C{C}]"
@@ -1477,7 +1395,7 @@ def _warp_backward(src, flow, dout, dsrc, dflow, galias, add_flow, flow_bound):
     L = _L()
     s16 = int(src.dtype == torch.bfloat16)
     if (WARP_TILES and dsrc is not None and not flow_bound and (C == 3 or not add_flow) and not (C == 3 and s16)
-            and dout.dtype == torch.float32 and B * D * H * W >= WARP_TILE_MIN_VOXELS):
+            and dout.dtype == torch.float32):
         nb = L.modet_warp_bwd_dsrc_tiles_ws_bytes(B, D, H, W, C)
         if nb:
             ws = _ws(nb, src)

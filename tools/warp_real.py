@@ -70,12 +70,12 @@ def main():
     model, mov, fix = setup()
     if mode == "step":
         variants = {}
-        for v, mv in ((False, 0), (True, 0), (True, 400_000)):
-            ops.WARP_TILES, ops.WARP_TILE_MIN_VOXELS = v, mv
+        for v in (False, True):
+            ops.WARP_TILES = v
             tr = Trainer(model)
             tr.capture(mov, fix)
-            variants[f"WARP_TILES={v} min_voxels={mv}"] = tr
-        ops.WARP_TILES, ops.WARP_TILE_MIN_VOXELS = True, 0
+            variants[f"WARP_TILES={v}"] = tr
+        ops.WARP_TILES = True
         for tr in variants.values():
             for _ in range(3):
                 tr._graph.replay()
