@@ -44,7 +44,8 @@ def conv_ins_block(p, name, x):
 
 
 def encoder(p, x, taps=None, tag=""):
-    """Five-level pyramid (ModeT/models.py:181-228).  ``taps`` receives every block output as ``enc{tag}.{lvl}.{i}``."""
+    """Five-level pyramid (ModeT/models.py:181-228).  ``taps`` receives every block output as ``enc{tag}.{lvl}.{i}`` and the
+    pooled tensor entering level 1-4 as ``enc{tag}.{lvl}.0`` (index 0 of the reference's Sequential: the AvgPool3d)."""
     def tap(name, t):
         if taps is not None:
             taps[f"enc{tag}.{name}"] = t
@@ -56,7 +57,7 @@ def encoder(p, x, taps=None, tag=""):
     outs = [o0]
     cur = o0
     for lvl in range(1, 5):
-        cur = F.avg_pool3d(cur, 2)
+        cur = tap(f"{lvl}.0", F.avg_pool3d(cur, 2))
         cur = tap(f"{lvl}.1", conv_ins_block(p, f"encoder.conv{lvl}.1", cur))
         cur = tap(f"{lvl}.2", conv_ins_block(p, f"encoder.conv{lvl}.2", cur))
         outs.append(cur)
@@ -217,6 +218,7 @@ def modet_forward(p, moving, fixed, num_heads=(8, 4, 2, 1, 1), head_dim=6, scale
     flow = warp(flow, w) + w
     y_moved = warp(moving, flow)
     if taps is not None:
+        taps["flow"], taps["y_moved"] = flow, y_moved
         for i in range(5):
             taps[f"M{i + 1}"], taps[f"F{i + 1}"] = M[i], Fx[i]
     return y_moved, flow

@@ -33,7 +33,17 @@ __device__ __forceinline__ float4 pool_dy_value(const float4 gv, const float4 av
   return r;
 }
 
+// The statistics pass over a sample of at most IN_SHIFT_MAX_V voxels sums x - K and (x - K)^2, K = the sample's first voxel, and
+// in_finalize_kernel adds K back.  var = E[x^2] - E[x]^2 from fp32 partial sums loses eps_f32 * mean^2 / (var + eps) of rstd.  A
+// channel's variance over V voxels has V - 1 degrees of freedom: over hundreds of voxels mean^2 / (var + eps) stays below 10
+// (conv outputs of normalised inputs), but on the 1x2x1-voxel level 5 of a 16x32x16 volume it reaches 800 -- rstd off by 1.4e-5,
+// the normalised tensor by 1.6e-5 where ATen fp32 is off by 5e-6, and, since that level feeds every other one, every stage
+// gradient of that volume by 4 - 19 x ATen's own error.  Shifted, the cancellation is against
+// (mean - K)^2 <= the sample's range squared.  Larger samples keep the plain sums (MODE 0), bit for bit.
+constexpr int64_t IN_SHIFT_MAX_V = 8;
+
 // MODE 0: (sum x, sum x^2)        MODE 1: (sum g, sum g*xhat), g = dy * lrelu'(xhat)        MODE 2: MODE 1 with d_y from PoolSrc
+// MODE 3: MODE 0 shifted, (sum x - K, sum (x - K)^2)
 template <int MODE>
 __global__ __launch_bounds__(BLK) void in_partial_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -47,9 +57,13 @@ __global__ __launch_bounds__(BLK) void in_partial_kernel(const float* __restrict
   const bool active = vl < VPB;
   float a[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
   float mu[4] = {0.f, 0.f, 0.f, 0.f}, rs[4] = {1.f, 1.f, 1.f, 1.f};
-  if (MODE >= 1 && active) {
+  if ((MODE == 1 || MODE == 2) && active) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) { mu[c] = mean[b * C + g * 4 + c]; rs[c] = rstd[b * C + g * 4 + c]; }
+  }
+  if (MODE == 3 && active) {                                // shifted sums (see IN_SHIFT_MAX_V): K = the sample's first voxel
+    const float4 k4 = *reinterpret_cast<const float4*>(x + (int64_t)b * V * C + g * 4);
+    mu[0] = k4.x; mu[1] = k4.y; mu[2] = k4.z; mu[3] = k4.w;
   }
   const int64_t v0 = (int64_t)blockIdx.x * chunk;
   const int64_t v1 = v0 + chunk < V ? v0 + chunk : V;
@@ -59,6 +73,9 @@ __global__ __launch_bounds__(BLK) void in_partial_kernel(const float* __restrict
       if (MODE == 0) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) { a[c] += xs[c]; q[c] = fmaf(xs[c], xs[c], q[c]); }
+      } else if (MODE == 3) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { const float d = xs[c] - mu[c]; a[c] += d; q[c] = fmaf(d, d, q[c]); }
       } else {
         const float gs[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
@@ -70,7 +87,7 @@ __global__ __launch_bounds__(BLK) void in_partial_kernel(const float* __restrict
       }
     };
     // the loads of PU passes are issued together, the sums keep their order (bit-identical to the one-pass-per-trip loop)
-    constexpr int PU = MODE == 0 ? 4 : 2;
+    constexpr int PU = (MODE == 0 || MODE == 3) ? 4 : 2;
     int64_t v = v0 + vl;
     for (; v + (PU - 1) * VPB < v1; v += PU * VPB) {
       float4 xv[PU], gv[PU], av[PU];
@@ -152,11 +169,12 @@ __global__ __launch_bounds__(BLK) void in_partial_kernel(const float* __restrict
   }
 }
 
-// MODE 0: -> mean, rstd.   MODE 1: -> (sum g)/V, (sum g*xhat)/V in out0/out1.
+// MODE 0: -> mean, rstd (x0: part holds the shifted sums of IN_SHIFT_MAX_V, K = x0[b][voxel 0][c]).   MODE 1: -> (sum g)/V, (sum g*xhat)/V in out0/out1.
 template <int MODE>
 __global__ __launch_bounds__(64) void in_finalize_kernel(const float* __restrict__ part, float* __restrict__ out0,
                                                          float* __restrict__ out1, int64_t V, int C, int nchunk, float eps,
-                                                         float* __restrict__ amax_zero = nullptr) {
+                                                         float* __restrict__ amax_zero = nullptr,
+                                                         const float* __restrict__ x0 = nullptr) {
   const int b = blockIdx.y, c = blockIdx.x;       // one wave per (b,c): fixed assignment + fixed tree, fp64
   if (amax_zero && b == 0 && c == 0) amax_zero[threadIdx.x * MODET_AMAX_STRIDE] = 0.f;   // (64 threads = MODET_AMAX_SLOTS) the apply pass maxes into them
   double s = 0.0, q = 0.0;
@@ -170,7 +188,7 @@ __global__ __launch_bounds__(64) void in_finalize_kernel(const float* __restrict
     const double m = s / (double)V;
     double var = q / (double)V - m * m;
     if (var < 0.0) var = 0.0;
-    out0[b * C + c] = (float)m;
+    out0[b * C + c] = (float)((x0 ? (double)x0[(int64_t)b * V * C + c] : 0.0) + m);
     out1[b * C + c] = (float)(1.0 / sqrt(var + (double)eps));
   } else {
     out0[b * C + c] = (float)(s / (double)V);
@@ -923,8 +941,9 @@ int modet_instnorm_lrelu_fwd(const float* x, float* y, float* mean, float* rstd,
   const int chunk = in_chunk(C);
   const int nchunk = (int)cdiv64(V, chunk);
   float* part = (float*)ws;
-  hipLaunchKernelGGL(in_partial_kernel<0>, dim3(nchunk, B), dim3(BLK), 0, s, x, nullptr, nullptr, nullptr, part, V, C, chunk);
-  hipLaunchKernelGGL(in_finalize_kernel<0>, dim3(C, B), dim3(64), 0, s, part, mean, rstd, V, C, nchunk, eps);
+  if (V <= IN_SHIFT_MAX_V) hipLaunchKernelGGL(in_partial_kernel<3>, dim3(nchunk, B), dim3(BLK), 0, s, x, nullptr, nullptr, nullptr, part, V, C, chunk);
+  else hipLaunchKernelGGL(in_partial_kernel<0>, dim3(nchunk, B), dim3(BLK), 0, s, x, nullptr, nullptr, nullptr, part, V, C, chunk);
+  hipLaunchKernelGGL(in_finalize_kernel<0>, dim3(C, B), dim3(64), 0, s, part, mean, rstd, V, C, nchunk, eps, (float*)nullptr, V <= IN_SHIFT_MAX_V ? x : (const float*)nullptr);
   const int64_t total4 = (int64_t)B * V * (C / 4);
   hipLaunchKernelGGL(in_apply_kernel, dim3(flat_grid(total4, BLK)), dim3(BLK), 0, s, x, y, mean, rstd, V, C, total4);
   return modet_launch_status();
@@ -972,8 +991,9 @@ int modet_instnorm_stats(const float* x, float* mean, float* rstd, const float* 
   const int chunk = in_chunk(C);
   const int nchunk = (int)cdiv64(V, chunk);
   float* part = (float*)ws;
-  hipLaunchKernelGGL(in_partial_kernel<0>, dim3(nchunk, B), dim3(BLK), 0, s, x, nullptr, nullptr, nullptr, part, V, C, chunk);
-  hipLaunchKernelGGL(in_finalize_kernel<0>, dim3(C, B), dim3(64), 0, s, part, mean, rstd, V, C, nchunk, eps);
+  if (V <= IN_SHIFT_MAX_V) hipLaunchKernelGGL(in_partial_kernel<3>, dim3(nchunk, B), dim3(BLK), 0, s, x, nullptr, nullptr, nullptr, part, V, C, chunk);
+  else hipLaunchKernelGGL(in_partial_kernel<0>, dim3(nchunk, B), dim3(BLK), 0, s, x, nullptr, nullptr, nullptr, part, V, C, chunk);
+  hipLaunchKernelGGL(in_finalize_kernel<0>, dim3(C, B), dim3(64), 0, s, part, mean, rstd, V, C, nchunk, eps, (float*)nullptr, V <= IN_SHIFT_MAX_V ? x : (const float*)nullptr);
   return modet_launch_status();
 }
 

@@ -873,7 +873,7 @@ def test_gradient_yardstick_scores_each_tensor_against_aten_fp32():
     """tests/util.grad_yardstick on the oracle's own fp64 / fp32 gradients at 16x32x16: the fp32 set passes as the candidate,
     the analytically-zero conv biases are not scored, and a candidate with ONE tensor scaled by 1 + 1e-3 (the size of error a
     kernel can add while every gradient stays inside the old flat 5e-3 bound) fails at A = GRAD_A, the message naming that
-    tensor and its two errors.  (The GPU test at this shape holds some tensors to a pinned A of their own: GRAD_A_OPEN.)"""
+    tensor and its two errors."""
     from tests.util import GRAD_A, GRAD_FLOOR, grad_yardstick, oracle_train_grads
     from smilecode_amd import synth
     w = synth.make_weights(24)
@@ -890,3 +890,69 @@ def test_gradient_yardstick_scores_each_tensor_against_aten_fp32():
     with pytest.raises(AssertionError, match=name.replace(".", r"\.") + r": e_hip 1\.\d+e-03, e_f32 "):
         grad_yardstick("selftest[16x32x16]", g64, g32, off, record=False)
     assert GRAD_A * res[name][1] + GRAD_FLOOR < 1e-3
+
+
+@pytest.mark.parametrize("shape,batch", [((16, 32, 16), 1), ((32, 32, 48), 3)])
+def test_local_vjp_segments_sum_to_the_end_to_end_gradient(shape, batch):
+    """tests/local_vjp.py cuts the oracle's forward + train loss into segments and hands each one its inputs and the cotangent
+    of every output; the GPU tests run one HIP op per segment on them.  That the cut is right is a chain-rule identity, checked
+    here in fp64 against an INDEPENDENT, uncut run of the oracle: for every cut tensor and every parameter, the sum of the local
+    VJPs of the segments that consume it equals autograd.grad of the train loss end to end.  (Level features 1-4 also feed the
+    next encoder level through the pool INSIDE their encoder group: there the heads' share the segments add up, plus the pool's
+    backward of the end-to-end gradient at the pooled tensor, equals the end-to-end total.)  The only slack is fp64 summation
+    order: 1e-10 of the tensor's max -- the oracle agrees with the reference to 4e-15 relative (tests/golden/REPORT*.txt), which
+    leaves five decades for reordered sums and is five decades below the 2e-5 floor the GPU tests work at.  Coverage by name:
+    every parameter is produced by exactly one segment, every tap the oracle records is an input of a segment, a second name of
+    such a tensor, or a group's interior block."""
+    import torch.nn.functional as F
+    from smilecode_amd import synth
+    from tests import local_vjp as lv
+    w = synth.make_weights(24)
+    mov, fix = synth.make_pair(shape, 31, batch)
+    segs, loss = lv.segments(w, mov, fix, HEADS, 6, 1.0)
+    p, taps, loss_e, _ = lv.oracle_taps(w, mov, fix, HEADS, 6, 1.0)
+    assert loss == float(loss_e.detach())
+    # ---- coverage
+    assert len({s.name for s in segs}) == len(segs) == 2 + 4 + 3 + 5 + 5 + 4 + 6
+    made = [n for s in segs for n in s.params]
+    assert sorted(made) == sorted(w), (set(w) - set(made), [n for n in made if made.count(n) > 1])
+    for second, first in lv.ALIASES.items():
+        assert taps[second] is taps[first], (second, first)
+    consumed = lv.consumed_taps(segs) - {"moving", "fixed", "images"}
+    assert not consumed & (set(lv.ALIASES) | set(lv.INTERIOR_TAPS))
+    assert consumed | set(lv.ALIASES) | set(lv.INTERIOR_TAPS) == set(taps), set(taps) ^ (consumed | set(lv.ALIASES) | set(lv.INTERIOR_TAPS))
+    # ---- the chain rule
+    names = sorted(consumed)
+    e2e = dict(zip(names, torch.autograd.grad(loss_e, [taps[n] for n in names], retain_graph=True)))
+    e2e.update(zip(p, torch.autograd.grad(loss_e, list(p.values()))))
+    local = {}
+    for s in segs:
+        outs, g = s.run(torch.float64)
+        if s.name == "loss":
+            assert float(outs[0]) == loss
+        for o, c in zip(outs, s.cots):
+            assert o.shape == c.shape, s.name
+        for n, gi in g.items():
+            local[n] = local[n] + gi if n in local else gi
+    scored = {"d." + n for s in segs for n in s.scored}
+    assert set(local) == scored | set(w)
+    assert {n[2:] for n in scored} == {("enc." + n[5:] if n.startswith("enc") else n) for n in consumed}, "every cut tensor is scored"
+    worst = 0.0
+    for n, got in local.items():
+        if not n.startswith("d."):
+            want = e2e[n]
+        elif n.startswith("d.enc."):
+            want = torch.cat([e2e["encM." + n[6:]], e2e["encF." + n[6:]]], 0)
+        else:
+            want = e2e[n[2:]]
+            if n[2] in "MF" and n[3:] in "1234":            # + the share that reaches the features through the pool
+                got = got + F.interpolate(e2e[f"enc{n[2]}.{n[3:]}.0"], scale_factor=2, mode="nearest") / 8
+        assert got.shape == want.shape, n
+        scale = float(want.abs().max())
+        err = float((got - want).abs().max())
+        if scale == 0.0:
+            assert err == 0.0, n
+            continue
+        worst = max(worst, err / scale)
+        assert err <= 1e-10 * scale, (n, err, scale)
+    print(f"local VJP chain rule {shape} B={batch}: worst {worst:.2e} of a tensor's max over {len(local)} tensors")

@@ -287,10 +287,12 @@ def test_forward_and_grads_vs_oracle_edge_shapes(shape, batch):
 STAGES = ("flow", "Mw1", "M1", "F1", "flow2", "Mw2", "M2", "F2", "flow3", "Mw3", "M3", "F3", "flow4", "Mw4", "M4", "F4", "flow5",
           "M5", "F5")
 # the stages HIP is measured beyond tests.util.GRAD_A x ATen fp32 on (e_f32: the worst of the F32_RUNS runs), each pinned at
-# 1.35 x its own measured (e_hip - floor) / e_f32 (open finding); every other stage is held to GRAD_A
+# 1.35 x its own measured (e_hip - floor) / e_f32 (open finding); every other stage is held to GRAD_A.
+# None is left: the 16 stages pinned at 4 - 26 at 16x32x16 (measured up to 18.9 on flow2) measure 1.4 and less since the
+# InstanceNorm statistics of a sample of two voxels -- that volume's level 5 -- are summed shifted (csrc/norm_act.hip
+# IN_SHIFT_MAX_V; found by test_local_vjp_vs_oracle below)
 STAGE_A = {
-    (16, 32, 16): {"Mw1": 8, "M1": 7, "flow2": 26, "Mw2": 6, "M2": 9, "F2": 7, "flow3": 11, "Mw3": 6, "M3": 4, "F3": 4, "flow4": 14,
-                   "Mw4": 10, "M4": 11, "F4": 8, "flow5": 7, "M5": 4},
+    (16, 32, 16): {},
     (48, 64, 48): {},
 }
 
@@ -350,6 +352,213 @@ def test_stage_gradients_vs_oracle(shape, monkeypatch):
         ghip[s] = g.permute(0, 4, 1, 2, 3)                     # channels-last -> the oracle's (B, C, D, H, W)
         assert tuple(ghip[s].shape) == tuple(ref[0][s].shape), (s, tuple(g.shape))
     grad_yardstick(f"stage[{'x'.join(map(str, shape))}]", ref[0], ref[1:], ghip, a=STAGE_A[shape], in_order=True)
+
+
+
+# ---- local vector-Jacobian products: every differentiable op of the path run ALONE on the oracle's own fp64 input tensors and
+# the oracle's own incoming gradient of that op (tests/local_vjp.py; the cut itself is checked on the host by
+# tests/test_cpu.py::test_local_vjp_segments_sum_to_the_end_to_end_gradient).  Nothing is inherited from the ops behind it in
+# the backward pass, so a segment over the bound IS the op that adds the error -- what the end-to-end and stage yardsticks
+# above cannot say.  (case: shape, pair seed, batch, configuration.)  The last case is the CONTROL: its stage test is clean
+# (STAGE_A[(48, 64, 48)] == {}), so it takes no pins.
+LOCAL_CASES = {
+    "16x32x16_B1": ((16, 32, 16), 31, 1, {}),
+    "32x32x48_B3": ((32, 32, 48), 31, 3, {}),
+    "heads_4_4_2": ((48, 64, 48), 24, 1, {"num_heads": [4, 4, 2, 1, 1]}),
+    "control_48x64x48": ((48, 64, 48), 24, 1, {}),
+}
+# (case -> segment -> tensor -> A) measured beyond tests.util.GRAD_A, pinned by GRAD_A_OPEN's convention.  Empty: every segment
+# of every case is held to GRAD_A.
+LOCAL_A_OPEN = {}
+
+
+@pytest.fixture(scope="module")
+def local_case():
+    """case name -> (model, B, [(segment on fp32-rounded tensors, fp64 outputs, fp64 VJP, [F32_RUNS fp32 VJPs])]): one fp64
+    oracle run per case and module, shared by the tests below"""
+    from smilecode_amd import synth
+    from tests import local_vjp
+    cache = {}
+
+    def get(case):
+        if case not in cache:
+            shape, seed, batch, kw = LOCAL_CASES[case]
+            _, _, head_dim, heads = _cfg(kw)
+            model, w = _cfg_model(shape, kw)
+            mov, fix = synth.make_pair(shape, seed, batch)
+            segs, _ = local_vjp.segments(w, mov, fix, heads, head_dim, kw.get("scale", 1.0))
+            rows = []
+            for s in segs:
+                s = s.rounded()
+                out64, g64 = s.run(torch.float64)
+                g32 = []
+                for run in range(F32_RUNS):
+                    ins = dict(zip(s.inputs, f32_inputs(list(s.inputs.values()), run)))
+                    g32.append(s.run(torch.float32, inputs=ins)[1])
+                rows.append((s, out64, g64, g32))
+            cache[case] = (model, batch, rows)
+        return cache[case]
+    return get
+
+
+def _local_expected_wgrads(case, seg):
+    """the conv weight-gradient launches (B, D, H, W, Cin, Cout) the FULL model makes for the layers of this segment, from the
+    case's shape, batch and configuration alone (Encoder.forward_pair: moving and fixed as one batch of 2B; CWM: at twice the
+    level's grid)"""
+    shape, _, B, kw = LOCAL_CASES[case]
+    _, c, _, heads = _cfg(kw)
+    L = seg.level
+    if seg.kind == "encoder_first":
+        return [(2 * B, *shape, 1, c)]
+    if seg.kind in ("encoder_group", "encoder_last"):
+        dims, cin, cout = [v >> L for v in shape], (c if L == 0 else c << L), c << (L + 1)
+        return [(2 * B, *dims, cout, cout), (2 * B, *dims, cin, cout)]
+    if seg.kind == "cwm":
+        dims, h = [v >> (L - 2) for v in shape], heads[5 - L]
+        return [(B, *dims, 6 * h, h), (B, *dims, 6 * h, 6 * h), (B, *dims, 3 * h, 6 * h)]
+    return []
+
+
+def _local_hip(model, B, seg, cots=None, launches=None):
+    """one segment on the product's own nodes -- the model's submodules and the ops.* autograd functions ModeT.forward_cl calls,
+    with the arguments of that level -- on cuda tensors made of the segment's fp32 inputs; returns (outputs, VJP) on the host
+    in the oracle's layouts and names.  ``launches`` (a list) receives the shape of every conv weight-gradient launch."""
+    from smilecode_amd import losses, models, ops
+    n, kind = seg.level, seg.kind
+    prm = dict(model.named_parameters())
+
+    def cl(t, grad=True):                          # the oracle's (B,C,D,H,W) -> cuda channels-last leaf
+        return t.float().cuda().permute(0, 2, 3, 4, 1).contiguous().requires_grad_(grad)
+
+    def back(t):
+        return t.permute(0, 4, 1, 2, 3)
+    ins = seg.inputs
+    ST = model.transformer
+    if kind == "loss":
+        fix = ins["fixed"].float().cuda()
+        leaves = [ins["y_moved"].float().cuda().requires_grad_(True), ins["flow"].float().cuda().requires_grad_(True)]
+        outs = [losses.NCC_vxm()(fix, leaves[0]) + losses.Grad3d(penalty="l2")(leaves[1], fix)]
+        o_back = g_back = lambda t: t
+    elif kind in ("attention", "projection"):
+        o_back = back if kind == "attention" else (lambda t: t)
+        if kind == "attention":                    # q, k: (B,D,H,W,dim) on both sides; the field comes back channels-last
+            leaves = [ins[f"q{n}"].float().cuda().requires_grad_(True), ins[f"k{n}"].float().cuda().requires_grad_(True)]
+            outs = [getattr(model, f"mdt{n}")(*leaves)]
+            g_back = lambda t: t
+        else:
+            leaves = [cl(ins[k]) for k in seg.scored]
+            outs = list(getattr(model, f"projblock{n}").forward_pair(*leaves))
+            g_back = back
+    else:
+        o_back = g_back = back
+        leaves = [cl(ins[k]) for k in seg.scored]
+        if kind == "image_warp":
+            outs = [ops.warp_tee(cl(ins["moving"], False), leaves[0])[0]]      # (the alias: the flow's other consumer, the loss segment)
+        elif kind == "feature_warp":
+            outs = [ops.warp_tee(*leaves)[0]]      # (the alias: the flow's other consumer, the composition segment)
+        elif kind == "compose":
+            fin, w = leaves
+            if n >= 3:
+                outs = [ST[n - 2].forward_cl(ops.upsample2(fin, 2.0), w, add_flow=True)]
+            elif n == 2:
+                outs = [ops.upsample2(ST[1].forward_cl(fin, w, add_flow=True, flow_bound=1), 2.0)]
+            else:
+                outs = [ST[0].forward_cl(fin, w, add_flow=True, flow_bound=1)]
+        elif kind == "cwm":
+            outs = [getattr(model, f"cwm{n}")(leaves[0])]
+        elif kind == "encoder_first":
+            outs = [model.encoder.conv0[0](cl(ins["images"], False))]
+        elif kind == "encoder_group":
+            blk = getattr(model.encoder, f"conv{n}")
+            outs = list(models._two_blocks_pool(leaves[0], blk[1], blk[2], B, x_act=n > 0))
+        elif kind == "encoder_last":
+            outs = [models._two_blocks(leaves[0], model.encoder.conv4[1], model.encoder.conv4[2], False)]
+        else:
+            raise AssertionError(kind)
+    cots = [c.float().cuda() for c in (seg.cots if cots is None else cots)]
+    cots = [c if kind in ("loss", "projection") else c.permute(0, 2, 3, 4, 1).contiguous() for c in cots]
+    real = ops.conv3d_backward_weight
+
+    def spy(x, dy, *a, **k):
+        launches.append((*x.shape[:4], x.shape[-1], dy.shape[-1]))
+        return real(x, dy, *a, **k)
+    if launches is not None:
+        ops.conv3d_backward_weight = spy
+    try:
+        g = torch.autograd.grad(outs, leaves + [prm[k] for k in seg.params], cots)
+    finally:
+        ops.conv3d_backward_weight = real
+    torch.cuda.synchronize()
+    grads = {"d." + k: g_back(gi).cpu() for k, gi in zip(seg.scored, g)}
+    grads.update({k: gi.cpu() for k, gi in zip(seg.params, g[len(leaves):])})
+    return [o_back(o.detach()).cpu() for o in outs], grads
+
+
+def _local_zero_biases(seg):
+    """the conv biases in front of an InstanceNorm among the segment's parameters: their gradient is analytically zero"""
+    return {k for k in seg.params if k.endswith(".main.bias") and k != "encoder.conv0.0.main.bias"}
+
+
+@pytest.mark.parametrize("case", list(LOCAL_CASES))
+def test_local_vjp_vs_oracle(case, local_case, monkeypatch):
+    """Every segment of the case (29: the loss, the image warp, per level the flow composition, the CWM, the attention, the
+    projection pair and the feature warp, and the encoder's six groups): the HIP nodes' forward against the fp64 closure at the
+    per-op tolerance (assert_close's default) and their VJP under the oracle's own cotangent against fp64, scored by
+    grad_yardstick against ATen fp32 on the same fp32-rounded tensors -- e_hip <= GRAD_A x e_f32 + GRAD_FLOOR, tag
+    local[<case>].<segment>.  ops.GRAD_F16 is at its default, so the kernel family, the f16 / bf16 piece form and the dy_amax
+    tags are the step's; the conv weight-gradient launches of a segment must be the full model's for those layers (and in the
+    B = 3 case the level-1 ones the z-marching family, 2).  All segments run; the failure lists every one that is off.  A
+    segment over the bound is run again with ops.GRAD_F16 = False and those errors are recorded beside it
+    (local[<case>].<segment>.bf16x3.*): they say whether the f16-piece form with its shared dy_amax adds the error."""
+    from smilecode_amd import ops
+    assert ops.GRAD_F16, "the step's default"
+    model, B, rows = local_case(case)
+    L = ops._L()
+    failures = []
+    for seg, out64, g64, g32 in rows:
+        tag = f"local[{case}].{seg.name}"
+        launches = []
+        outs, ghip = _local_hip(model, B, seg, launches=launches)
+        assert sorted(launches) == sorted(_local_expected_wgrads(case, seg)), (tag, launches)
+        if case == "32x32x48_B3" and seg.name == "encoder0":
+            assert [L.modet_conv3d_kernel_family_v(*s, 2, 0) for s in sorted(launches)] == [2, 2], "the batch-routed z-marching weight gradient"
+            assert [L.modet_conv3d_kernel_family_v(2, *s[1:], 2, 0) for s in sorted(launches)] == [4, 4], "(B = 1 at this shape: conv_wgrad_tr_kernel)"
+        for name, o, ref in zip(seg.out_names, outs, out64):
+            try:
+                assert_close(o.double().numpy(), ref.numpy(), what=f"{tag}: forward {name}")
+            except AssertionError as e:
+                failures.append(str(e))
+        zero = _local_zero_biases(seg)
+        for k in zero:
+            assert float(g64[k].abs().max()) < 1e-8 and float(ghip[k].abs().max()) < 1e-5, (tag, k, float(ghip[k].abs().max()))
+        try:
+            res = grad_yardstick(tag, g64, g32, ghip, a=LOCAL_A_OPEN.get(case, {}).get(seg.name, {}))
+            assert set(g64) - set(res) == zero, (tag, set(g64) - set(res))
+        except AssertionError as e:
+            failures.append(str(e))
+            monkeypatch.setattr(ops, "GRAD_F16", False)
+            _, g3 = _local_hip(model, B, seg)
+            monkeypatch.setattr(ops, "GRAD_F16", True)
+            from tests.util import note_many, rel_err
+            note_many({f"{tag}.bf16x3.{k}.e_hip": rel_err(g3[k], ref) for k, ref in g64.items() if k not in zero})
+    assert not failures, f"{len(failures)} of {len(rows)} segments off:\n" + "\n".join(failures)
+
+
+@pytest.mark.parametrize("case", list(LOCAL_CASES))
+def test_local_vjp_flags_a_bf16_rounded_cotangent(case, local_case):
+    """the test above must be able to fail: the HIP VJP of the level-1 attention and of the level-2 encoder group computed from
+    the cotangent rounded to bf16 -- a 2^-9 relative error, below the end-to-end outer bound of 5e-3 and far above fp32's --
+    is reported as over the bound by the same scoring, against the same fp64 and fp32 results.  (The level-2 group, not the
+    level-1 one: there ATen fp32's OWN error reaches 6e-3 in the B = 3 case -- LeakyReLU kink flips, DESIGN.md section 2 --
+    which is more than the 2^-9 injected here, so no scoring against that yardstick could flag it.)"""
+    model, B, rows = local_case(case)
+    assert {"attention1", "encoder1"} <= {seg.name for seg, _, _, _ in rows}
+    for seg, _, g64, g32 in rows:
+        if seg.name not in ("attention1", "encoder1"):
+            continue
+        _, ghip = _local_hip(model, B, seg, cots=[c.bfloat16().float() for c in seg.cots])
+        with pytest.raises(AssertionError, match="gradient error beyond"):
+            grad_yardstick(f"local[{case}].{seg.name}", g64, g32, ghip, a=LOCAL_A_OPEN.get(case, {}).get(seg.name, {}), record=False)
 
 
 # ---- configurations other than the default ModeT(channels=4, head_dim=6, num_heads=[8,4,2,1,1]): each runs kernels the

@@ -841,6 +841,32 @@ def test_instnorm_backward_leaves_the_gradient_maximum(ops):
     assert tag2 is not None and float(tag2[::32].max()) == float(dx2.abs().max())
 
 
+@pytest.mark.parametrize("shape", [(1, 2, 1), (1, 2, 2), (2, 2, 2)])
+def test_instnorm_statistics_of_a_few_voxels_beside_a_large_mean(ops, shape):
+    """InstanceNorm over 2, 4 and 8 voxels -- level 5 of a 16x32x16, 16x32x32, 32x32x32 volume -- of channels whose |mean| is 0.1 - 0.4,
+    30 - 120 x sqrt(var + eps) (over so few voxels a channel's variance falls far below its squared mean: 800 x at level 5 of the
+    16x32x16 edge case): the normalised tensor at the per-op tolerance, mean and rstd against fp64 of the same fp32 values.
+    var = E[x^2] - E[x]^2 from fp32 sums loses eps_f32 * mean^2 / (var + eps) of rstd, up to 9e-4 here and as much of the output; the
+    shifted sums of csrc/norm_act.hip (IN_SHIFT_MAX_V) cancel against the sample's range instead.  rstd's bound: (x - K)^2 <=
+    16 var, <= 10 roundings on the way -> 160 eps_f32 * var / (var + eps) on var + eps, half of it on rstd, < 1e-6."""
+    gen = torch.Generator().manual_seed(sum(shape))
+    B, C = 3, 64
+    sign = torch.where(torch.rand((B, C, 1, 1, 1), generator=gen) < 0.5, -1.0, 1.0)
+    x = (sign * (0.1 + 0.3 * torch.rand((B, C, 1, 1, 1), generator=gen)) + 1e-3 * torch.randn((B, C) + shape, generator=gen)).float()
+    x64 = x.double()
+    ref = torch.nn.functional.leaky_relu(torch.nn.functional.instance_norm(x64, eps=1e-5), 0.1)
+    m64 = x64.mean((2, 3, 4)).reshape(-1)
+    r64 = (x64.var((2, 3, 4), unbiased=False) + 1e-5).rsqrt().reshape(-1)
+    assert float((m64 * r64).abs().max()) > 100, "mean^2 >> var + eps"
+    xd = cl(x.numpy())
+    assert_close(ncdhw(ops.instnorm_lrelu(xd)), ref.numpy(), what="InstanceNorm + LeakyReLU over %d voxels" % int(np.prod(shape)))
+    mean, rstd = ops.instnorm_stats(xd)
+    assert_close(np64(mean), m64.numpy(), atol=1e-7, rtol=1e-7, what="mean")
+    e = float((rstd.double().cpu() / r64 - 1).abs().max())
+    _note("instnorm_few_voxels[%d].rstd_relerr" % int(np.prod(shape)), e)
+    assert e < 1e-6, e
+
+
 @pytest.mark.parametrize("Cin,Cout,shape,xs,ws", [(32, 32, (40, 48, 40), 1.0, 1.0), (16, 32, (40, 48, 40), 30.0, 0.05), (64, 64, (20, 24, 20), 2e-3, 4.0),
                                                   (24, 48, (20, 24, 28), 1.0, 1.0), (6, 12, (40, 48, 56), 0.5, 1.0), (32, 64, (20, 24, 20), 200.0, 1.0),
                                                   # cfg 5's level-3 CWM layers: 1.72 M voxels (beyond the round-4 routing limit of 1.5 M)

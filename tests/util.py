@@ -92,7 +92,6 @@ GRAD_A_OPEN = {
     "config[heads_4_4_2]": {"cwm4.conv.1.main.weight": 7.0, "encoder.conv0.0.main.bias": 4.0},
     "config[operator_heads_4_4_2,fused=0]": {"cwm4.conv.1.main.weight": 7.0, "encoder.conv0.0.main.bias": 4.0},
     "config[operator_heads_4_4_2,fused=1]": {"cwm4.conv.1.main.weight": 7.0, "encoder.conv0.0.main.bias": 4.0},
-    "edge[16x32x16_B1]": {"mdt1.rpb": 4.0, "projblock1.norm.weight": 4.0},
     "edge[32x32x48_B3]": {"encoder.conv0.0.main.bias": 23.0, "encoder.conv0.0.main.weight": 13.0,
                           "encoder.conv0.1.main.weight": 7.0, "encoder.conv0.2.main.weight": 17.0,
                           "encoder.conv1.1.main.weight": 43.0},
