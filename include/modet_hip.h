@@ -397,7 +397,19 @@ int modet_proj_ln_bwd_pair_t(const void* x1, int x1_bf16, const float* d_y1, flo
  *   (the reference's normalise -> grid_sample(align_corners=True) round trip is the identity).
  * src,out (B,D,H,W,C); flow (B,D,H,W,3) channels-last, component a = displacement along axis a.
  * mode 0 = trilinear, 1 = nearest (round half to even, as ATen's nearbyint).
- * add_flow=1 (needs C==3): out = warp(src,flow) + flow, the composition of models.py:392,:398,:403,:408. */
+ * add_flow=1 (needs C==3): out = warp(src,flow) + flow, the composition of models.py:392,:398,:403,:408.
+ * FLOW VALUES AND ADDRESSES (every warp entry point below, forward and backward, and modet_label_warp_counts): a flow's values
+ * become indices, so each kernel bounds the base corner while it is still a float (clamped to [-2, 1e9] / compared against the
+ * dimensions before the conversion to int): a displacement of any magnitude -- 1e9, 3e38 -- is simply "outside the volume", with
+ * the results a displacement of 1e4 gives (0 output, 0 gradient, nothing scattered), and no address outside the tensors is
+ * formed.  A NON-FINITE displacement (NaN, +-inf) reads and writes nothing outside the tensors either and contributes nothing to
+ * d_src.  What the voxel ITSELF receives (pinned by tests/test_gpu_guard.py, not a promise of ATen parity):
+ *   out, trilinear (modet_warp_fwd mode 0, _o16, _t):   NaN in every channel (the weights are NaN; with add_flow too)
+ *   out, nearest (mode 1) and the warped label:          0 (no comparison with NaN holds: outside)
+ *   d_flow of modet_warp_bwd / _acc / _det:              NaN in at least one component of the voxel, the others carry no
+ *                                                        contribution of this warp (d_flow_add, + d_out with add_flow)
+ *   d_flow of modet_warp_bwd_tiles:                      the voxel is dropped while binning: d_flow_add (+ d_out with add_flow)
+ * Every other voxel is unaffected.  modet_warp_bwd with flow_bound=1 carries the caller's promise |flow| <= 1 instead. */
 int modet_warp_fwd(const float* src, const float* flow, float* out, int B, int D, int H, int W, int C,
                    int mode, int add_flow, modet_stream_t stream);
 /* trilinear warp whose OUTPUT is stored as bf16 (rounded to nearest even; BASELINE.json configs[4]: the warped moving features
@@ -436,7 +448,13 @@ int modet_warp_bwd_det(const void* src, int src_bf16, const float* flow, const f
  * LDS window (2^-40 of the power of two above max |d_out| per unit, as modet_warp_bwd_det) -> BORDER gather of the tile faces.  Equal to modet_warp_bwd
  * within fp32 rounding of the sums (the float-atomic ORDER is what differs there run to run; this one is bit-reproducible: integer
  * sums), every launch a kernel with fixed arguments (capturable).  d_src need NOT be zeroed; the workspace needs no preparation.
- * A non-finite d_out poisons d_src with NaN (as the float path would).  C a multiple of 8, or C == 3 (fp32 src; the flow
+ * A non-finite d_out poisons d_src with NaN -- GLOBALLY: the fixed-point scale comes from max |d_out| over the whole tensor, so
+ * ONE NaN or inf in a kept d_out voxel (one whose corners reach the volume) turns d_src of every non-empty tile into NaN, where the
+ * float-atomic path spoils the eight corners of that voxel only.  Headroom of the 64-bit window: a unit is 2^-40 of the power of
+ * two above max |d_out|, so a cell's int64 sum holds 2^23 terms of maximum size (weights <= 1) before it wraps; nothing guards
+ * this, and B*D*H*W may be up to 2^31 -- a flow that sends more than 8.4 million maximum-size contributions into ONE cell is
+ * outside what the kernel computes correctly (a whole 160x192x160 volume collapsing onto a voxel stays below it: 4.9 M).
+ * C a multiple of 8, or C == 3 (fp32 src; the flow
  * compositions warp(src, flow) + flow with add_flow != 0: d_flow += d_out); dimensions <= 1024, B*D*H*W < 2^31; _ws_bytes returns
  * 0 for anything else (then: modet_warp_bwd_acc / modet_warp_bwd_det).
  * modet_warp_bwd_dsrc_tiles: d_src only.  modet_warp_bwd_tiles: d_src and d_flow (+ d_flow_add, NULL = none: a second gradient
@@ -547,6 +565,9 @@ int modet_jacdet_nonpos_count(const float* flow, int64_t* counts, double* det_ou
  * conv_x3_wgrad_kernel<.., NPC = 1>): the few-channel full-resolution layers, HBM-bound */
 int modet_conv3d_bf16_kernel_family(int B, int D, int H, int W, int Cin, int Cout, int pass, int x_bf16);
 size_t modet_conv3d_bf16_ws_bytes(int Cin, int Cout);
+/* Layout of the statistics buffer: a [sample][Cout] shift header, one row [Cout][2] per (sample, output tile), and a TAIL of 64
+ * rows per sample that modet_conv3d_bf16_fwd does NOT write: it is scratch of the first reduction stage of the consuming
+ * modet_instnorm_lrelu_fwd_stats_bf16.  After the conv alone the tail holds whatever the allocation held. */
 size_t modet_conv3d_bf16_stats_bytes(int B, int D, int H, int W, int Cin, int Cout);
 int modet_conv3d_bf16_fwd(const void* x, int x_bf16, const float* w, const float* bias, void* y, void* ws, size_t ws_bytes,
                           float* stats, size_t stats_bytes, int B, int D, int H, int W, int Cin, int Cout,

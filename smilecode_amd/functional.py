@@ -30,17 +30,31 @@ def _same_dtype(ref, *others):
     return "_f64" if ref.dtype == torch.float64 else ""
 
 
-def modet_fw(query, key, rpb=None):
-    _check_input(query, "query"); _check_input(key, "key")
+def _qk_args(op, query, key):
+    """query (B,heads,D,H,W,d), key its zero-padded partner on the same device"""
+    if query.dim() != 6:
+        raise RuntimeError(f"{op}: query must be (B,heads,D,H,W,d), got {tuple(query.shape)}")
     B, heads, D, H, W, d = query.shape
     if tuple(key.shape) != (B, heads, D + 2, H + 2, W + 2, d):
-        raise RuntimeError("key must be the zero-padded (B,heads,D+2,H+2,W+2,d) tensor")
+        raise RuntimeError(f"{op}: key must be the zero-padded (B,heads,D+2,H+2,W+2,d) tensor, got {tuple(key.shape)} for query "
+                           f"{tuple(query.shape)}")
+    if key.device != query.device:     # (two GPUs: a host tensor is refused by _check_input before; so are rpb's and d_attn's device below)
+        raise RuntimeError(f"{op}: key lives on {key.device}, query on {query.device}")
     if min(D, H, W) < 3:
         raise RuntimeError("Input resolution must be greater than or equal to kernel size.")   # utils.h:10
+    return B, heads, D, H, W, d
+
+
+def modet_fw(query, key, rpb=None):
+    _check_input(query, "query"); _check_input(key, "key")
+    B, heads, D, H, W, d = _qk_args("modet_fw", query, key)
     if rpb is not None:
         _check_input(rpb, "rpb")
-        if rpb.shape[1] != 3:
-            raise RuntimeError("modet_fw does not support kernel size %d" % rpb.shape[1])
+        if rpb.dim() != 4 or rpb.shape[1] != 3:
+            raise RuntimeError("modet_fw does not support kernel size %d" % (rpb.shape[1] if rpb.dim() > 1 else 0))
+        if tuple(rpb.shape) != (heads, 3, 3, 3) or rpb.device != query.device:
+            raise RuntimeError(f"modet_fw: rpb {tuple(rpb.shape)} on {rpb.device} does not match the (heads,3,3,3) of query "
+                               f"{tuple(query.shape)} on {query.device}")
     sfx = _same_dtype(query, key, rpb)
     attn = torch.empty((B, heads, D, H, W, 27), dtype=query.dtype, device=query.device)
     with _Guard(query):
@@ -51,7 +65,10 @@ def modet_fw(query, key, rpb=None):
 
 def modet_bw(d_attn, query, key, biasEnabled):
     _check_input(d_attn, "d_attn"); _check_input(query, "query"); _check_input(key, "key")
-    B, heads, D, H, W, d = query.shape
+    B, heads, D, H, W, d = _qk_args("modet_bw", query, key)
+    if tuple(d_attn.shape) != (B, heads, D, H, W, 27) or d_attn.device != query.device:
+        raise RuntimeError(f"modet_bw: d_attn {tuple(d_attn.shape)} on {d_attn.device} does not match the (B,heads,D,H,W,27) of "
+                           f"query {tuple(query.shape)} on {query.device}")
     d_query, d_key = torch.empty_like(query), torch.empty_like(key)
     sfx = _same_dtype(query, key, d_attn)
     d_rpb = torch.empty((heads, 3, 3, 3), dtype=query.dtype, device=query.device) if biasEnabled else None

@@ -44,6 +44,33 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _same_shape(op, name, t, want, of=""):
+    """refuse a tensor whose shape the kernel would otherwise infer from another argument (None passes: an absent operand)"""
+    if t is not None and tuple(t.shape) != tuple(want):
+        raise RuntimeError(f"{op}: {name} {tuple(t.shape)} does not match {tuple(want)}" + (f" ({of})" if of else ""))
+
+
+def _rank5(op, name, t):
+    """the kernels take channels-last (B,D,H,W,C) tensors: refuse another rank by name instead of failing to unpack the shape"""
+    if t.dim() != 5:
+        raise RuntimeError(f"{op}: {name} must be a channels-last (B,D,H,W,C) tensor, got {tuple(t.shape)}")
+
+
+def _amax_arg(op, amax):
+    """a gradient-maximum buffer is read (and by the InstanceNorm backward written) over all its AMAX_FLOATS floats"""
+    if amax is not None and amax.numel() < AMAX_FLOATS:
+        raise RuntimeError(f"{op}: amax {tuple(amax.shape)} holds fewer than the {AMAX_FLOATS} floats of a gradient-maximum buffer")
+
+
+def _conv_args(op, x, w, b):
+    """x (B,D,H,W,Cin), w (Cout,Cin,3,3,3), b (Cout,) or None"""
+    if x.dim() != 5 or w.dim() != 5:
+        raise RuntimeError(f"{op}: expects a channels-last (B,D,H,W,Cin) input and a (Cout,Cin,3,3,3) weight, got "
+                           f"{tuple(x.shape)} and {tuple(w.shape)}")
+    _same_shape(op, "weight", w, (w.shape[0], x.shape[-1], 3, 3, 3), f"input {tuple(x.shape)}")
+    _same_shape(op, "bias", b, (w.shape[0],), f"weight {tuple(w.shape)}")
+
+
 def _ws(nbytes, like):
     return torch.empty((int(nbytes) + 3) // 4 + 1, dtype=torch.float32, device=like.device)
 
@@ -197,11 +224,13 @@ def conv3d_forward(x, w, b, act, step=None, x_act=False):
     |x| < 4 094) -> the *_bounded entry point, half the matrix work; without it the launch makes no assumption about x (three
     bf16 pieces: fp32's range), as nn.Conv3d makes none"""
     _chk(x, w, b)
+    _rank5("conv3d", "the input", x)
     step = step if step is not None else current_step()
     B, D, H, W, Cin = x.shape
     Cout = w.shape[0]
     if tuple(w.shape) != (Cout, Cin, 3, 3, 3):
         raise RuntimeError(f"conv3d: weight {tuple(w.shape)} does not match input channels {Cin}")
+    _same_shape("conv3d", "bias", b, (Cout,), f"weight {tuple(w.shape)}")
     y = torch.empty((B, D, H, W, Cout), dtype=torch.float32, device=x.device)
     L = _L()
     nb = L.modet_conv3d_ws_bytes(Cin, Cout)
@@ -237,10 +266,13 @@ def instnorm_stats(x_raw, stats=None, eps=1e-5):
 def conv3d_forward_normin(x_raw, mean, rstd, w, b, want_stats=True, step=None):
     """conv3d(LeakyReLU((x_raw - mean) * rstd), w, b) with the normalisation applied while the input tile is staged;
     returns (y, stats or None)"""
-    _chk(x_raw, w, b)
+    _chk(x_raw, mean, rstd, w, b)
+    _conv_args("conv3d_forward_normin", x_raw, w, b)
     step = step if step is not None else current_step()
     B, D, H, W, Cin = x_raw.shape
     Cout = w.shape[0]
+    _same_shape("conv3d_forward_normin", "mean", mean, (B * Cin,), f"input {tuple(x_raw.shape)}")
+    _same_shape("conv3d_forward_normin", "rstd", rstd, (B * Cin,), f"input {tuple(x_raw.shape)}")
     L = _L()
     y = torch.empty((B, D, H, W, Cout), dtype=torch.float32, device=x_raw.device)
     nb = L.modet_conv3d_ws_bytes(Cin, Cout)
@@ -300,9 +332,13 @@ def _amax_of(t):
 
 
 def conv3d_backward_data(dy, w, Cin, step=None, amax=None):
-    _chk(dy, w)
+    _chk(dy, w, amax)
     step = step if step is not None else current_step()
+    if dy.dim() != 5:
+        raise RuntimeError(f"conv3d_backward_data: expects a channels-last (B,D,H,W,Cout) gradient, got {tuple(dy.shape)}")
     B, D, H, W, Cout = dy.shape
+    _same_shape("conv3d_backward_data", "weight", w, (Cout, Cin, 3, 3, 3), f"gradient {tuple(dy.shape)}, Cin {Cin}")
+    _amax_arg("conv3d_backward_data", amax)
     dx = torch.empty((B, D, H, W, Cin), dtype=torch.float32, device=dy.device)
     L = _L()
     nb = L.modet_conv3d_ws_bytes(Cin, Cout)
@@ -509,9 +545,17 @@ def conv3d_backward_weight(x, dy, want_bias, y_act=None, w=None, b=None, step=No
     (None, None) is returned.  amax: one-float tensor >= max |dy| (see _tag_amax) and the caller's word that x is an
     activation: the z-marching kernel then runs on two f16 pieces.  norm = (mean, rstd): x is a RAW ConvInsBlock output,
     normalised while the kernel stages it (only where the library's *_normin_ok says so)."""
-    _chk(x, dy)
+    _chk(x, dy, y_act, amax)
+    if x.dim() != 5 or dy.dim() != 5 or tuple(dy.shape[:4]) != tuple(x.shape[:4]):
+        raise RuntimeError(f"conv3d_backward_weight: gradient {tuple(dy.shape)} does not match input {tuple(x.shape)}")
     B, D, H, W, Cin = x.shape
     Cout = dy.shape[-1]
+    _same_shape("conv3d_backward_weight", "y_act", y_act, dy.shape, "the gradient")
+    _amax_arg("conv3d_backward_weight", amax)
+    if norm is not None:
+        _chk(*norm)
+        _same_shape("conv3d_backward_weight", "mean", norm[0], (B * Cin,), f"input {tuple(x.shape)}")
+        _same_shape("conv3d_backward_weight", "rstd", norm[1], (B * Cin,), f"input {tuple(x.shape)}")
     L = _L()
     nb = L.modet_conv3d_bwd_weight_ws_bytes(B, D, H, W, Cin, Cout)
     n = float(B) * D * H * W
@@ -589,6 +633,7 @@ class _Conv3dStats(Function):
     @staticmethod
     def forward(ctx, x, w, b, x_act=False):
         _chk(x, w, b)
+        _conv_args("conv3d_with_stats", x, w, b)
         ctx.step = current_step()
         ctx.x_act = bool(x_act)                 # x is an activation (bounded: see modet_conv3d_bwd_weight_amax)
         B, D, H, W, Cin = x.shape
@@ -654,6 +699,7 @@ def lazy_instnorm_conv3d(x_raw, stats_in, w, b, eps=1e-5, want_stats=True):
     conv's epilogue (or one statistics pass) and the conv kernel normalises its input tile while staging it (-3.5 % on the
     forward pass).  With gradients the tensor is needed by the weight gradient anyway (normalising on the fly there was
     measured slower), so the block runs as InstanceNorm + conv."""
+    _conv_args("lazy_instnorm_conv3d", x_raw, w, b)          # (before the statistics launch of the inference form)
     Cin = x_raw.shape[-1]
     needs_grad = torch.is_grad_enabled() and (x_raw.requires_grad or w.requires_grad)
     if not needs_grad and Cin % 4 == 0 and Cin > 1:
@@ -681,7 +727,8 @@ class _InstNormConv(Function):
 
     @staticmethod
     def forward(ctx, x_raw, stats_in, w, b, eps, want_stats):
-        _chk(x_raw, w, b)
+        _chk(x_raw, stats_in, w, b)
+        _conv_args("lazy_instnorm_conv3d", x_raw, w, b)
         ctx.step = current_step()
         B, C = x_raw.shape[0], x_raw.shape[-1]
         V = x_raw.numel() // (B * C)
@@ -843,6 +890,7 @@ class _AvgPool2(Function):
     @staticmethod
     def forward(ctx, x):
         _chk(x)
+        _rank5("avgpool2", "x", x)
         B, D, H, W, C = x.shape
         y = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
         with _Guard(x, "avgpool2_fwd", x.numel(), 4.5 * x.numel()):
@@ -873,6 +921,7 @@ class _PoolTee(Function):
     @staticmethod
     def forward(ctx, x):
         _chk(x)
+        _rank5("pool_tee", "x", x)
         B, D, H, W, C = x.shape
         y = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
         with _Guard(x, "avgpool2_fwd", x.numel(), 4.5 * x.numel()):
@@ -906,7 +955,10 @@ class _PoolTeeSplit(Function):
     @staticmethod
     def forward(ctx, x, Bh):
         _chk(x)
+        _rank5("pool_tee_split", "x", x)
         B, D, H, W, C = x.shape
+        if not 0 < Bh < B:
+            raise RuntimeError(f"pool_tee_split: split {Bh} is not inside the batch of {tuple(x.shape)}")
         y = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
         with _Guard(x, "avgpool2_fwd", x.numel(), 4.5 * x.numel()):
             _lib.check(_L().modet_avgpool2_fwd(_p(x), _p(y), B, D, H, W, C, _stream()), "modet_avgpool2_fwd")
@@ -949,8 +1001,11 @@ class _InstNormLReLUPoolSplit(Function):
 
     @staticmethod
     def forward(ctx, x, eps, stats, Bh):
-        _chk(x)
+        _chk(x, stats)
+        _rank5("instnorm_lrelu_pool_tee_split", "x_raw", x)
         B, D, H, W, C = x.shape
+        if not 0 < Bh < B:
+            raise RuntimeError(f"instnorm_lrelu_pool_tee_split: split {Bh} is not inside the batch of {tuple(x.shape)}")
         V = D * H * W
         L = _L()
         mean = torch.empty(B * C, dtype=torch.float32, device=x.device)
@@ -1013,12 +1068,22 @@ def instnorm_lrelu_pool_tee_split(x_raw, stats, Bh, eps=1e-5):
     return _InstNormLReLUPoolSplit.apply(x_raw, eps, stats, Bh)
 
 
+def _proj_args(op, Cin, Wt, b, gamma, beta):
+    """Wt (dim, Cin); b, gamma, beta (dim,)"""
+    if Wt.dim() != 2:
+        raise RuntimeError(f"{op}: expects a (dim, Cin) weight, got {tuple(Wt.shape)}")
+    _same_shape(op, "weight", Wt, (Wt.shape[0], Cin), f"input channels {Cin}")
+    for name, t in (("bias", b), ("gamma", gamma), ("beta", beta)):
+        _same_shape(op, name, t, (Wt.shape[0],), f"weight {tuple(Wt.shape)}")
+
+
 class _ProjLN(Function):
     @staticmethod
     def forward(ctx, x, Wt, b, gamma, beta, eps):
         _chk(x, Wt, b, gamma, beta)
         Cin = x.shape[-1]
         dim = Wt.shape[0]
+        _proj_args("proj_ln", Cin, Wt, b, gamma, beta)
         N = x.numel() // Cin
         y = torch.empty(x.shape[:-1] + (dim,), dtype=torch.float32, device=x.device)
         with _Guard(x, f"proj_ln_fwd[{Cin}->{dim}]", N * (2.0 * Cin * dim + 8.0 * dim), 4.0 * N * (Cin + dim)):
@@ -1060,6 +1125,8 @@ class _ProjLNPair(Function):
         _chk(x1, x2, Wt, b, gamma, beta)
         Cin = x1.shape[-1]
         dim = Wt.shape[0]
+        _same_shape("proj_ln_pair", "x2", x2, x1.shape, "x1")
+        _proj_args("proj_ln_pair", Cin, Wt, b, gamma, beta)
         N = x1.numel() // Cin
         L = _L()
         ys = [torch.empty(x.shape[:-1] + (dim,), dtype=torch.float32, device=x.device) for x in (x1, x2)]
@@ -1111,14 +1178,30 @@ def proj_ln(x, Wt, b, gamma, beta, eps=1e-5):
     return _ProjLN.apply(x, Wt, b, gamma, beta, eps)
 
 
+def _na_args(op, C, heads, rpb, bf16):
+    """head_dim of C channels in ``heads`` heads; rpb holds heads * 27 biases.  The kernels: head_dim 6 (fused), and in fp32 any
+    multiple of 8 up to 128 (csrc/na.hip gen_hd_ok)."""
+    heads = int(heads)
+    if heads < 1 or C % heads != 0:
+        raise RuntimeError(f"{op}: {C} channels do not split into {heads} heads")
+    hd = C // heads
+    if hd != 6 and (bf16 or hd % 8 != 0 or hd > 128):
+        raise RuntimeError(f"{op}: head_dim {hd} is not supported (6" + ("" if bf16 else ", or a multiple of 8 up to 128") + ")")
+    if rpb.numel() != heads * 27:
+        raise RuntimeError(f"{op}: rpb {tuple(rpb.shape)} does not hold {heads} x 27 biases")
+    return hd
+
+
 class _NA(Function):
     @staticmethod
     def forward(ctx, q, k, rpb, heads, scale):
         _chk(q, k, rpb)
+        if q.dim() != 5:
+            raise RuntimeError(f"neighbourhood attention: expects channels-last (B,D,H,W,heads*head_dim) q and k, got {tuple(q.shape)}")
         B, D, H, W, C = q.shape
         if k.shape != q.shape:
             raise RuntimeError("neighbourhood attention: q and k shapes differ")
-        hd = C // heads
+        hd = _na_args("neighbourhood attention", C, heads, rpb, False)
         out = torch.empty((B, D, H, W, heads * 3), dtype=torch.float32, device=q.device)
         need_grad = any(ctx.needs_input_grad[:3])
         lse = torch.empty((B, D, H, W, heads), dtype=torch.float32, device=q.device) if need_grad else None
@@ -1170,8 +1253,13 @@ class _LevelAttnBF16(Function):
         ctx.set_materialize_grads(False)
         ctx.step = current_step()
         ctx.beta_ref = beta                  # (only its address and shape: the key of its gradient destination)
+        _rank5("level attention (bf16)", "F", F)
         B, D, H, W, Cin = F.shape
         dim = Wt.shape[0]
+        _same_shape("level attention (bf16)", "M", M, F.shape, "F")
+        _same_shape("level attention (bf16)", "flow", flow, (B, D, H, W, 3), f"F {tuple(F.shape)}")
+        _proj_args("level attention (bf16)", Cin, Wt, b, gamma, beta)
+        _na_args("level attention (bf16)", dim, heads, rpb, True)
         N = B * D * H * W
         L = _L()
         n = float(N)
@@ -1181,6 +1269,8 @@ class _LevelAttnBF16(Function):
         Fd = F if Fd is None else Fd
         Md = M if Md is None else Md
         _chk16(Fd, Md)
+        _same_shape("level attention (bf16)", "F's bf16 data", Fd, F.shape, "F")
+        _same_shape("level attention (bf16)", "M's bf16 data", Md, M.shape, "M")
         m16 = int(Md.dtype == torch.bfloat16)
         if flow is not None:
             _chk(flow)
@@ -1280,6 +1370,8 @@ class _Corr3d(Function):
     @staticmethod
     def forward(ctx, mov, fix):
         _chk(mov, fix)
+        if mov.dim() != 5:
+            raise RuntimeError(f"correlation3d: expects channels-last (B,D,H,W,C) features, got {tuple(mov.shape)}")
         B, D, H, W, C = mov.shape
         if fix.shape != mov.shape:
             raise RuntimeError("correlation3d: mov and fix shapes differ")
@@ -1323,6 +1415,7 @@ class _Warp(Function):
     @staticmethod
     def forward(ctx, src, flow, mode, add_flow, flow_bound=0):
         _chk(src, flow)
+        _rank5("warp", "src", src)
         B, D, H, W, C = src.shape
         if tuple(flow.shape) != (B, D, H, W, 3):
             raise RuntimeError(f"warp: flow {tuple(flow.shape)} does not match src {tuple(src.shape)}")
@@ -1425,6 +1518,7 @@ class _WarpTee(Function):
     @staticmethod
     def forward(ctx, src, flow):
         _chk(src, flow)
+        _rank5("warp", "src", src)
         B, D, H, W, C = src.shape
         if tuple(flow.shape) != (B, D, H, W, 3):
             raise RuntimeError(f"warp: flow {tuple(flow.shape)} does not match src {tuple(src.shape)}")
@@ -1477,6 +1571,7 @@ class _Upsample2(Function):
     @staticmethod
     def forward(ctx, x, scale):
         _chk(x)
+        _rank5("upsample2", "x", x)
         B, d, h, w, C = x.shape
         y = torch.empty((B, 2 * d, 2 * h, 2 * w, C), dtype=torch.float32, device=x.device)
         with _Guard(x, f"upsample2_fwd[C{C}]", 16.0 * y.numel(), 4.0 * (x.numel() + y.numel())):
@@ -1513,6 +1608,7 @@ class _CwmTail(Function):
     def forward(ctx, x, logits):
         _chk(x, logits)
         heads = logits.shape[-1]
+        _same_shape("cwm_tail", "x", x, tuple(logits.shape[:-1]) + (heads * 3,), f"logits {tuple(logits.shape)}: heads * 3 channels")
         N = logits.numel() // heads
         out = torch.empty(logits.shape[:-1] + (3,), dtype=torch.float32, device=x.device)
         with _Guard(x, "cwm_tail_fwd", 12.0 * x.numel(), 4.0 * (x.numel() + logits.numel() + out.numel())):
@@ -1736,6 +1832,9 @@ def grad3d_value_and_grad_cl(flow_cl, penalty="l2", grad_scale=1.0):
 def adam_amsgrad_step_(p, g, m, v, vmax, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
     """in-place Adam(amsgrad=True) over flat buffers.  reference: train.py:101,:131-133"""
     _chk(p, g, m, v, vmax)
+    for name, t in (("g", g), ("m", m), ("v", v), ("vmax", vmax)):
+        if t.numel() != p.numel():
+            raise RuntimeError(f"adam_amsgrad_step_: {name} {tuple(t.shape)} does not match p {tuple(p.shape)}")
     with _Guard(p, "adam_amsgrad", 12.0 * p.numel(), 28.0 * p.numel()):
         _lib.check(_L().modet_adam_amsgrad_step(_p(p), _p(g), _p(m), _p(v), _p(vmax), p.numel(), float(lr), beta1,
                                                 beta2, eps, int(step), float(grad_scale), _stream()),
@@ -1748,7 +1847,17 @@ def label_warp_counts(lab_moving, flow_cl, lab_fixed, nlabels=54, want_warped=Tr
     if lab_moving.dtype != torch.int16 or lab_fixed.dtype != torch.int16:
         raise RuntimeError("label_warp_counts: labels must be int16")
     _chk(flow_cl)
+    if lab_moving.dim() < 3 or lab_moving.numel() != lab_moving.shape[-3] * lab_moving.shape[-2] * lab_moving.shape[-1]:
+        raise RuntimeError(f"label_warp_counts: lab_moving {tuple(lab_moving.shape)} is not one (D,H,W) volume")
     D, H, W = lab_moving.shape[-3:]
+    if lab_fixed.dim() < 3 or tuple(lab_fixed.shape[-3:]) != (D, H, W) or lab_fixed.numel() != D * H * W:
+        raise RuntimeError(f"label_warp_counts: lab_fixed {tuple(lab_fixed.shape)} does not match lab_moving {tuple(lab_moving.shape)}")
+    _same_shape("label_warp_counts", "flow_cl", flow_cl, (1, D, H, W, 3), f"lab_moving {tuple(lab_moving.shape)}: one sample")
+    for name, t in (("lab_moving", lab_moving), ("lab_fixed", lab_fixed)):
+        if t.device != flow_cl.device:
+            raise RuntimeError(f"label_warp_counts: {name} lives on {t.device}, flow_cl on {flow_cl.device}")
+    if int(nlabels) < 1:
+        raise RuntimeError(f"label_warp_counts: nlabels {nlabels} is not positive")
     lm, lf = lab_moving.contiguous(), lab_fixed.contiguous()
     warped = torch.empty((D, H, W), dtype=torch.int16, device=lm.device) if want_warped else None
     counts = torch.empty((3, nlabels + 1), dtype=torch.int64, device=lm.device)
@@ -1763,6 +1872,8 @@ def jacdet_nonpos_count(flow_cl, want_det=False):
     reference's fp64 operation order (utils.py:108-150, infer.py:89-90).  flow_cl (B,D,H,W,3) channels-last fp32.
     Returns (counts int64 (B,), det float64 (B,D,H,W) or None)."""
     _chk(flow_cl)
+    if flow_cl.dim() != 5:
+        raise RuntimeError(f"jacdet_nonpos_count: expects a (B,D,H,W,3) channels-last flow, got {tuple(flow_cl.shape)}")
     B, D, H, W, C = flow_cl.shape
     if C != 3:
         raise RuntimeError("jacdet_nonpos_count: expects a (B,D,H,W,3) channels-last flow")
@@ -1807,11 +1918,13 @@ def conv3d_bf16_forward(x, w, b, want_stats=True, step=None):
     """y (bf16) = conv3d(x (fp32 | bf16), w) + b on the bf16 matrix pipe, fp32 accumulate; (y, stats | None)"""
     _chk16(x)
     _chk(w, b)
+    _rank5("conv3d_bf16", "the input", x)
     step = step if step is not None else current_step()
     B, D, H, W, Cin = x.shape
     Cout = w.shape[0]
     if tuple(w.shape) != (Cout, Cin, 3, 3, 3):
         raise RuntimeError(f"conv3d_bf16: weight {tuple(w.shape)} does not match input channels {Cin}")
+    _same_shape("conv3d_bf16", "bias", b, (Cout,), f"weight {tuple(w.shape)}")
     L = _L()
     y = torch.empty((B, D, H, W, Cout), dtype=torch.bfloat16, device=x.device)
     nb = L.modet_conv3d_bf16_ws_bytes(Cin, Cout)
@@ -1829,7 +1942,10 @@ def conv3d_bf16_backward_data(dy, w, Cin, dx_bf16, step=None):
     _chk16(dy)
     _chk(w)
     step = step if step is not None else current_step()
+    if dy.dim() != 5:
+        raise RuntimeError(f"conv3d_bf16_backward_data: expects a channels-last (B,D,H,W,Cout) gradient, got {tuple(dy.shape)}")
     B, D, H, W, Cout = dy.shape
+    _same_shape("conv3d_bf16_backward_data", "weight", w, (Cout, Cin, 3, 3, 3), f"gradient {tuple(dy.shape)}, Cin {Cin}")
     dx = torch.empty((B, D, H, W, Cin), dtype=torch.bfloat16 if dx_bf16 else torch.float32, device=dy.device)
     L = _L()
     nb = L.modet_conv3d_bf16_ws_bytes(Cin, Cout)
@@ -1845,6 +1961,10 @@ def conv3d_bf16_backward_weight(x, dy, w=None, b=None, step=None):
     """d_w, d_bias (fp32) from x (fp32 | bf16) and d_y (bf16); with a StepContext whose ``deferred()`` scope has
     destinations for the parameters ``w`` / ``b`` the gradients go there at the flush and (None, None) is returned"""
     _chk16(x, dy)
+    if x.dim() != 5 or dy.dim() != 5 or tuple(dy.shape[:4]) != tuple(x.shape[:4]):
+        raise RuntimeError(f"conv3d_bf16_backward_weight: gradient {tuple(dy.shape)} does not match input {tuple(x.shape)}")
+    if dy.dtype != torch.bfloat16:
+        raise RuntimeError(f"conv3d_bf16_backward_weight: the gradient must be bfloat16, got {dy.dtype}")
     L = _L()
     if hasattr(L, "modet_conv3d_bf16_bwd_weight"):
         B, D, H, W, Cin = x.shape
@@ -1905,6 +2025,9 @@ class _InstNormLReLUBF16(Function):
         _chk16(x)
         if x.dtype != torch.bfloat16:
             raise RuntimeError("instnorm bf16: the raw conv output must be bfloat16")
+        if stats is None:
+            raise RuntimeError("instnorm bf16: needs the conv epilogue's partial statistics")
+        _chk(stats)
         B, C = x.shape[0], x.shape[-1]
         V = x.numel() // (B * C)
         y = torch.empty(x.shape, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=x.device)
@@ -1947,7 +2070,13 @@ class _InstNormLReLUBF16PoolSplit(Function):
         _chk16(x)
         if x.dtype != torch.bfloat16:
             raise RuntimeError("instnorm bf16: the raw conv output must be bfloat16")
+        if stats is None:
+            raise RuntimeError("instnorm bf16: needs the conv epilogue's partial statistics")
+        _chk(stats)
+        _rank5("instnorm bf16", "the raw conv output", x)
         B, D, H, W, C = x.shape
+        if not 0 < Bh < B:
+            raise RuntimeError(f"instnorm bf16: split {Bh} is not inside the batch of {tuple(x.shape)}")
         V = D * H * W
         L = _L()
         y = torch.empty(x.shape, dtype=torch.bfloat16 if features16 else torch.float32, device=x.device)

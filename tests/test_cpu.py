@@ -956,3 +956,133 @@ def test_local_vjp_segments_sum_to_the_end_to_end_gradient(shape, batch):
         worst = max(worst, err / scale)
         assert err <= 1e-10 * scale, (n, err, scale)
     print(f"local VJP chain rule {shape} B={batch}: worst {worst:.2e} of a tensor's max over {len(local)} tensors")
+
+
+# ------------------------------------------------------------------------------------------------ the guard-band harness
+@pytest.fixture
+def guard():
+    from tests import guard as g
+    g.release()
+    yield g
+    g.release()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float64, torch.int16, torch.int64])
+def test_guard_reports_a_write_one_element_outside_with_side_and_distance(guard, dtype):
+    src = (torch.arange(2 * 3 * 5 * 7 * 4) % 50).to(dtype).reshape(2, 3, 5, 7, 4)
+    t = guard.guarded(src)
+    assert t.dtype == dtype and t.shape == src.shape and t.is_contiguous() and torch.equal(t, src)
+    assert t.data_ptr() % 512 == 0
+    assert guard.band_elems(src.shape) == 4096 and guard.band_elems((1, 2, 80, 90, 8)) == 80 * 90 * 8 and guard.band_elems((5000, 3)) == 4096
+    assert guard.band_elems((2, 9000)) == 9000
+    buf = guard.live()[-1]
+    item = src.element_size()
+    assert buf.off >= 4096 * item and buf.whole.numel() - buf.off - buf.nbytes >= 4096 * item
+    assert int((buf.whole[:buf.off] != 0xFF).sum()) == 0 and int((buf.whole[buf.off + buf.nbytes:] != 0xFF).sum()) == 0
+    assert guard.check() == []
+    flat = buf.whole.view(dtype)                       # the whole allocation as elements: the interior starts at off / item
+    first = buf.off // item
+    # reading the band: NaN for the floating types, -1 for the integer ones
+    below, above = flat[first - 1], flat[first + src.numel()]
+    for v in (below, above):
+        assert (torch.isnan(v) if dtype.is_floating_point else v == -1)
+    flat[first - 1] = 3
+    (d,) = guard.check()
+    assert d["side"] == "below" and d["distance"] == 1 and d["distance_bytes"] <= item and d["interior"] == src.numel()
+    assert "test_cpu.py" in d["site"] and d["dtype"] == str(dtype) and 1 <= d["bytes"] <= item
+    assert guard.check() == [], "check() re-arms the bands"
+    flat[first + src.numel()] = 3
+    flat[first + src.numel() + 9] = 3
+    (d,) = guard.check()
+    assert d["side"] == "above" and d["distance"] == 1 and "above" in guard.describe([d])
+    flat[first + src.numel() + 9] = 3
+    (d,) = guard.check()
+    assert d["side"] == "above" and d["distance"] == 10
+    assert torch.equal(t, src), "the interior is untouched by all of this"
+    with pytest.raises(AssertionError, match="damaged guard bands"):
+        flat[first - 2] = 0
+        guard.assert_intact("case")
+
+
+def test_guarded_alloc_poisons_empty_and_restores_torch(guard):
+    orig = (torch.empty, torch.empty_like, torch.zeros, torch.zeros_like, torch.full, torch.full_like)
+    with guard.GuardedAlloc(device_type="cpu"):
+        assert torch.empty is not orig[0]
+        e = torch.empty((3, 5), dtype=torch.float32, device="cpu")
+        e16 = torch.empty(7, dtype=torch.bfloat16, device=torch.device("cpu"))
+        ei = torch.empty_like(torch.ones(4, dtype=torch.int64))
+        z = torch.zeros(2, 3, dtype=torch.float64, device="cpu")
+        zl = torch.zeros_like(e)
+        f = torch.full((4,), 2.5, dtype=torch.float32, device="cpu")
+        n = len(guard.live())
+        plain = torch.empty(3, 5)                                      # names no device: the original
+        pinned = torch.zeros(3, dtype=torch.float32, device="cpu", requires_grad=True)   # more than shape/dtype/device: the original
+        strided = torch.empty_like(torch.ones(4, 6).t())               # not contiguous: the original
+        assert len(guard.live()) == n == 6
+    assert (torch.empty, torch.empty_like, torch.zeros, torch.zeros_like, torch.full, torch.full_like) == orig
+    assert torch.isnan(e).all() and e.shape == (3, 5) and torch.isnan(e16.float()).all() and bool((ei == -1).all())
+    assert bool((z == 0).all()) and z.dtype == torch.float64 and bool((zl == 0).all()) and bool((f == 2.5).all())
+    assert plain.shape == (3, 5) and pinned.requires_grad and strided.shape == (6, 4)
+    assert guard.check() == []
+    e.view(-1)[14] = 1.0                                               # the last interior element: no damage
+    assert guard.check() == []
+    with guard.GuardedAlloc(device_type="cpu", canary=0x00):          # the second run of a comparison: zero bands and interiors
+        e0 = torch.empty(5, dtype=torch.float32, device="cpu")
+    assert bool((e0 == 0).all()) and guard.check() == []
+    with pytest.raises(ValueError):
+        with guard.GuardedAlloc(device_type="cpu"):
+            raise ValueError("inside")
+    assert torch.empty is orig[0] and torch.zeros_like is orig[3], "restored on exceptions too"
+
+
+def test_lib_proxy_records_classifies_and_refuses(guard):
+    P, I = ctypes.c_void_p, ctypes.c_int
+    sig = {"modet_thing_fwd": (I, [P, P, P, I, P]), "modet_thing_ws_bytes": (ctypes.c_size_t, [I]),
+           "modet_hip_version": (I, []), "modet_thing_kernel_family_v": (I, [I])}
+
+    class Fake:
+        def __init__(self):
+            self.calls = []
+            self.other = 17
+
+        def modet_thing_fwd(self, *a):
+            self.calls.append(a)
+            return 0
+
+        def modet_thing_ws_bytes(self, n):
+            return 4 * n
+
+        def modet_hip_version(self):
+            return 3
+
+        def modet_thing_kernel_family_v(self, n):
+            return 1
+
+    fake = Fake()
+    t = guard.guarded(torch.zeros(10))
+    plain = torch.zeros(10)
+    segs = lambda: [(plain.data_ptr(), 40)]
+    px = guard.LibProxy(fake, signatures=sig, segments=segs)
+    assert px.other == 17 and px.modet_thing_fwd.__name__ == "modet_thing_fwd"
+    assert px.modet_thing_fwd(t.data_ptr(), t.data_ptr() + 12, plain.data_ptr() + 4, 5, None) == 0
+    assert px.modet_thing_fwd(0, ctypes.c_void_p(t.data_ptr()), t.data_ptr() + 40, 5, 0xdead0000) == 0
+    assert len(fake.calls) == 2
+    assert px.records == [("modet_thing_fwd", ["guarded", "guarded", "torch", "null"]),
+                          ("modet_thing_fwd", ["null", "guarded", "other", "other"])]      # (one past the interior's end: not guarded)
+    assert px.names() == {"modet_thing_fwd"} and px.calls == []
+    px.log_args = True                                                # the arguments themselves, for tests that ask what a call was given
+    px.modet_thing_fwd(None, None, None, 7, None)
+    assert px.calls == [("modet_thing_fwd", (None, None, None, 7, None))] and len(fake.calls) == 3
+    px.log_args = False
+    del px.records[2:], fake.calls[2:]
+    px.refuse = True
+    assert px.modet_thing_ws_bytes(3) == 12 and px.modet_hip_version() == 3 and px.modet_thing_kernel_family_v(1) == 1
+    with pytest.raises(AssertionError, match="modet_thing_fwd"):
+        px.modet_thing_fwd(t.data_ptr(), None, None, 5, None)
+    assert len(fake.calls) == 2, "refuse mode raises before forwarding"
+    from smilecode_amd import _lib
+    launching = [n for n in _lib.SIGNATURES if guard.is_launching(n)]
+    assert "modet_na_bwd_partial_rows" not in launching and "modet_step_ctx_create" not in launching
+    assert "modet_conv3d_prepack_begin" in launching and "modet_lrelu_bwd" in launching and len(launching) >= 80
+    assert not guard.is_query("modet_step_ctx_create") and guard.is_query("modet_qk_bwd_ws_bytes_f64")
+    assert guard.is_query("modet_conv3d_wgrad_defers_operands") and guard.is_query("modet_conv3d_bwd_weight_normin_ok")

@@ -2,6 +2,8 @@
 reference (tests/golden/*.npz, fp64) and (b) the CPU oracle (oracle/modet_torch.py) on odd, ragged shapes.
 All calls go through the C ABI (smilecode_amd.ops -> libmodet_hip.so).  Tolerance: fp32 kernels vs an fp64
 reference, |err| <= 2e-5 + 2e-5*|ref| per element unless a test states otherwise (sums over many voxels)."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -1683,10 +1685,168 @@ def test_label_warp_dice_golden(ops):
     assert abs(float(dice_val_VOI(lm[None, None], lf[None, None])) - float(g["dice_raw"])) < 1e-9
 
 
-def test_errors_are_loud(ops):
+def _Z(*shape, dtype=torch.float32, device="cuda"):
+    return torch.zeros(*shape, dtype=dtype, device=device)
+
+
+def _handle(like, data16):
+    """an fp32 feature handle carrying bf16 data (ops._InstNormLReLUBF16PoolSplit, features16)"""
+    h = torch.zeros(1, device="cuda").expand(like.shape)
+    h.data16 = data16
+    return h
+
+
+def _refusals():
+    """(the op's name as its message carries it, the call with mismatched arguments).  Every row is a tensor whose shape, dtype
+    or device a kernel would infer from ANOTHER argument: the host must refuse it before it takes a pointer."""
+    from smilecode_amd import functional as fn, losses, ops, utils
+    bf = torch.bfloat16
+    x8, w88, b8 = _Z(1, 4, 6, 8, 8), _Z(8, 8, 3, 3, 3), _Z(8)
+    lab = _Z(4, 6, 8, dtype=torch.int16)
+    q6 = _Z(1, 1, 4, 5, 6, 6)
+    k6 = _Z(1, 1, 6, 7, 8, 6)
+    pw = (_Z(6, 8), _Z(6), _Z(6), _Z(6))
+    g = lambda t: t.requires_grad_(True)
+    return [
+        # ---- the checks this table was written for
+        ("label_warp_counts", lambda: ops.label_warp_counts(lab, _Z(1, 4, 6, 8, 3), _Z(4, 6, 7, dtype=torch.int16))),      # lab_fixed of another shape
+        ("label_warp_counts", lambda: ops.label_warp_counts(lab, _Z(1, 4, 6, 9, 3), lab)),                                 # flow of another shape
+        ("label_warp_counts", lambda: ops.label_warp_counts(lab, _Z(2, 4, 6, 8, 3), lab)),                                 # a batch of flows
+        ("label_warp_counts", lambda: ops.label_warp_counts(lab.cpu(), _Z(1, 4, 6, 8, 3), lab)),                           # labels on the host
+        ("label_warp_counts", lambda: ops.label_warp_counts(lab, _Z(1, 4, 6, 8, 3), lab.cpu())),
+        ("label_warp_counts", lambda: ops.label_warp_counts(_Z(2, 4, 6, 8, dtype=torch.int16), _Z(1, 4, 6, 8, 3), lab)),   # two label volumes
+        ("label_warp_counts", lambda: ops.label_warp_counts(lab, _Z(1, 4, 6, 8, 3), lab, nlabels=0)),
+        ("label_warp_counts", lambda: utils.dice_val_VOI(_Z(1, 1, 4, 6, 8), _Z(1, 1, 4, 6, 9))),
+        ("neighbourhood attention", lambda: ops.neighbourhood_attention(_Z(1, 4, 4, 4, 12), _Z(1, 4, 4, 4, 12), _Z(1, 27), 2, 1.0)),   # short rpb
+        ("neighbourhood attention", lambda: ops.neighbourhood_attention(_Z(1, 4, 4, 4, 13), _Z(1, 4, 4, 4, 13), _Z(2, 27), 2, 1.0)),   # C % heads
+        ("neighbourhood attention", lambda: ops.neighbourhood_attention(_Z(1, 4, 4, 4, 7), _Z(1, 4, 4, 4, 7), _Z(1, 27), 1, 1.0)),     # head_dim 7
+        ("neighbourhood attention", lambda: ops.neighbourhood_attention(_Z(4, 4, 4, 6), _Z(4, 4, 4, 6), _Z(1, 27), 1, 1.0)),           # no batch axis
+        ("neighbourhood attention", lambda: ops.neighbourhood_attention(_Z(1, 4, 4, 4, 6), _Z(1, 4, 4, 5, 6), _Z(1, 27), 1, 1.0)),
+        ("cwm_tail", lambda: ops.cwm_tail(_Z(1, 100, 6), _Z(1, 100, 4))),                                                  # x is not (..., heads * 3)
+        ("cwm_tail", lambda: ops.cwm_tail(_Z(1, 99, 12), _Z(1, 100, 4))),
+        ("modet_fw", lambda: fn.modet_fw(_Z(1, 2, 4, 5, 6, 6), _Z(1, 2, 6, 7, 8, 6), _Z(1, 3, 3, 3))),                    # rpb of fewer heads
+        ("modet_fw", lambda: fn.modet_fw(_Z(2, 4, 5, 6, 6), _Z(2, 6, 7, 8, 6))),
+        ("modet_bw", lambda: fn.modet_bw(_Z(1, 1, 4, 5, 6, 26), q6, k6, True)),                                            # d_attn of another shape
+        ("modet_bw", lambda: fn.modet_bw(_Z(1, 1, 4, 5, 6, 27), q6, _Z(1, 1, 6, 7, 7, 6), True)),                          # key that is not query's partner
+        ("Input resolution", lambda: fn.modet_bw(_Z(1, 1, 2, 5, 6, 27), _Z(1, 1, 2, 5, 6, 6), _Z(1, 1, 4, 7, 8, 6), False)),   # smaller than the kernel
+        # ---- what the audit of ops.py found besides
+        ("conv3d", lambda: ops.conv3d(x8, w88, _Z(4))),                                                                   # bias of another size
+        ("conv3d_forward_normin", lambda: ops.conv3d_forward_normin(x8, _Z(4), _Z(8), w88, b8)),                           # mean of another size
+        ("conv3d_forward_normin", lambda: ops.conv3d_forward_normin(x8, _Z(8), _Z(8), _Z(8, 4, 3, 3, 3), b8)),
+        ("conv3d_backward_data", lambda: ops.conv3d_backward_data(x8, _Z(8, 4, 3, 3, 3), 8)),
+        ("conv3d_backward_weight", lambda: ops.conv3d_backward_weight(x8, _Z(1, 4, 6, 9, 8), True)),
+        ("conv3d_backward_weight", lambda: ops.conv3d_backward_weight(x8, x8, True, y_act=_Z(1, 4, 6, 8, 4))),
+        ("conv3d_backward_weight", lambda: ops.conv3d_backward_weight(x8, x8, True, amax=_Z(64 * 32), norm=(_Z(8), _Z(4)))),
+        ("conv3d", lambda: ops.conv3d_with_stats(x8, _Z(8, 4, 3, 3, 3), b8)),
+        ("conv3d_with_stats", lambda: ops._Conv3dStats.apply(x8, _Z(8, 4, 3, 3, 3), b8, False)),
+        ("lazy_instnorm_conv3d", lambda: ops.lazy_instnorm_conv3d(x8, None, _Z(8, 4, 3, 3, 3), b8)),                       # inference form
+        ("lazy_instnorm_conv3d", lambda: ops.lazy_instnorm_conv3d(g(_Z(1, 4, 6, 8, 8)), None, w88, _Z(4))),                # training form
+        ("pool_tee_split", lambda: ops.pool_tee_split(_Z(2, 4, 6, 8, 8), 2)),
+        ("instnorm_lrelu_pool_tee_split", lambda: ops.instnorm_lrelu_pool_tee_split(_Z(2, 4, 6, 8, 8), None, 0)),
+        ("proj_ln", lambda: ops.proj_ln(_Z(1, 50, 8), _Z(6, 4), *pw[1:])),
+        ("proj_ln", lambda: ops.proj_ln(_Z(1, 50, 8), pw[0], pw[1], _Z(5), pw[3])),
+        ("proj_ln", lambda: ops.proj_ln_pair(g(_Z(1, 50, 8)), g(_Z(1, 50, 8)), pw[0], pw[1], pw[2], _Z(12))),
+        ("level attention (bf16)", lambda: ops.level_attention_bf16(x8, _Z(1, 4, 6, 9, 8), None, *pw, _Z(1, 27), 1, 1.0)),
+        ("level attention (bf16)", lambda: ops.level_attention_bf16(x8, x8, _Z(1, 4, 6, 8, 2), *pw, _Z(1, 27), 1, 1.0)),
+        ("level attention (bf16)", lambda: ops.level_attention_bf16(x8, x8, None, *pw, _Z(1, 26), 1, 1.0)),
+        ("level attention (bf16)", lambda: ops.level_attention_bf16(x8, x8, None, _Z(8, 8), _Z(8), _Z(8), _Z(8), _Z(1, 27), 1, 1.0)),   # head_dim 8 in bf16
+        ("adam_amsgrad_step_", lambda: ops.adam_amsgrad_step_(_Z(100), _Z(99), _Z(100), _Z(100), _Z(100), 1e-3, 1)),
+        ("conv3d_bf16", lambda: ops.conv3d_bf16_forward(x8, w88, _Z(4))),
+        ("conv3d_bf16_backward_data", lambda: ops.conv3d_bf16_backward_data(_Z(1, 4, 6, 8, 8, dtype=bf), _Z(8, 4, 3, 3, 3), 8, True)),
+        ("conv3d_bf16_backward_weight", lambda: ops.conv3d_bf16_backward_weight(x8, _Z(1, 4, 6, 9, 8, dtype=bf))),
+        ("conv3d_bf16_backward_weight", lambda: ops.conv3d_bf16_backward_weight(x8, x8)),                                  # fp32 gradient
+        ("instnorm bf16", lambda: ops._InstNormLReLUBF16.apply(_Z(1, 4, 6, 8, 8, dtype=bf), None, 1e-5, True)),
+        # ---- one row per remaining added check (a check without a row could be deleted unseen)
+        ("label_warp_counts", lambda: ops.label_warp_counts(_Z(6, 8, dtype=torch.int16), _Z(1, 4, 6, 8, 3), lab)),         # fewer than three axes
+        ("conv3d_forward_normin", lambda: ops.conv3d_forward_normin(x8, _Z(8), _Z(4), w88, b8)),                           # rstd of another size
+        ("conv3d_forward_normin", lambda: ops.conv3d_forward_normin(_Z(4, 6, 8, 8), _Z(8), _Z(8), w88, b8)),               # 4-D input
+        ("conv3d_backward_data", lambda: ops.conv3d_backward_data(_Z(4, 6, 8, 8), w88, 8)),                                # 4-D gradient
+        ("conv3d_backward_data", lambda: ops.conv3d_backward_data(x8, w88, 8, amax=_Z(1))),                                # one float of amax
+        ("conv3d_backward_weight", lambda: ops.conv3d_backward_weight(x8, x8, True, amax=_Z(64))),
+        ("conv3d_backward_weight", lambda: ops.conv3d_backward_weight(x8, x8, True, amax=_Z(64 * 32), norm=(_Z(4), _Z(8)))),   # mean
+        ("conv3d_backward_weight", lambda: ops.conv3d_backward_weight(_Z(4, 6, 8, 8), _Z(4, 6, 8, 8), True)),
+        ("conv3d", lambda: ops.conv3d(_Z(4, 6, 8, 8), w88, b8)),                                                          # 4-D input
+        ("conv3d_with_stats", lambda: ops._Conv3dStats.apply(x8, w88, _Z(4), False)),
+        ("lazy_instnorm_conv3d", lambda: ops._InstNormConv.apply(g(_Z(1, 4, 6, 8, 8)), None, _Z(8, 4, 3, 3, 3), b8, 1e-5, True)),
+        ("avgpool2", lambda: ops.avgpool2(_Z(4, 6, 8, 8))),
+        ("pool_tee", lambda: ops.pool_tee(_Z(4, 6, 8, 8))),
+        ("pool_tee_split", lambda: ops.pool_tee_split(_Z(4, 6, 8, 8), 1)),
+        ("pool_tee_split", lambda: ops.pool_tee_split(_Z(2, 4, 6, 8, 8), 0)),
+        ("instnorm_lrelu_pool_tee_split", lambda: ops.instnorm_lrelu_pool_tee_split(_Z(4, 6, 8, 8), None, 1)),
+        ("instnorm_lrelu_pool_tee_split", lambda: ops.instnorm_lrelu_pool_tee_split(_Z(2, 4, 6, 8, 8), None, 2)),
+        ("smilecode_amd", lambda: ops.instnorm_lrelu_pool_tee_split(_Z(2, 4, 6, 8, 8), _Z(64).cpu(), 1)),                   # statistics on the host
+        ("smilecode_amd", lambda: ops.lazy_instnorm_conv3d(g(_Z(1, 4, 6, 8, 8)), _Z(64).cpu(), w88, b8)),
+        ("smilecode_amd", lambda: ops.conv3d_forward_normin(x8, _Z(8).cpu(), _Z(8), w88, b8)),
+        ("smilecode_amd", lambda: ops.conv3d_backward_data(x8, w88, 8, amax=_Z(64 * 32).cpu())),
+        ("smilecode_amd", lambda: ops.conv3d_backward_weight(x8, x8, True, y_act=x8.cpu())),
+        ("smilecode_amd", lambda: ops.conv3d_backward_weight(x8, x8, True, amax=_Z(64 * 32), norm=(_Z(8).cpu(), _Z(8)))),
+        ("proj_ln", lambda: ops.proj_ln(_Z(1, 50, 8), _Z(6, 8, 1), *pw[1:])),                                              # a 3-D weight
+        ("proj_ln", lambda: ops.proj_ln(_Z(1, 50, 8), pw[0], _Z(5), pw[2], pw[3])),                                        # bias
+        ("proj_ln", lambda: ops.proj_ln(_Z(1, 50, 8), pw[0], pw[1], pw[2], _Z(5))),                                        # beta
+        ("proj_ln_pair", lambda: ops._ProjLNPair.apply(_Z(1, 50, 8), _Z(1, 49, 8), *pw, 1e-5)),
+        ("proj_ln_pair", lambda: ops._ProjLNPair.apply(_Z(1, 50, 8), _Z(1, 50, 8), _Z(6, 4), *pw[1:], 1e-5)),
+        ("neighbourhood attention", lambda: ops.neighbourhood_attention(_Z(1, 4, 4, 4, 6), _Z(1, 4, 4, 4, 6), _Z(1, 27), 0, 1.0)),     # no heads
+        ("neighbourhood attention", lambda: ops.neighbourhood_attention(_Z(1, 4, 4, 4, 136), _Z(1, 4, 4, 4, 136), _Z(1, 27), 1, 1.0)),  # head_dim > 128
+        ("level attention (bf16)", lambda: ops.level_attention_bf16(_Z(4, 6, 8, 8), _Z(4, 6, 8, 8), None, *pw, _Z(1, 27), 1, 1.0)),   # 4-D features
+        ("level attention (bf16)", lambda: ops.level_attention_bf16(x8, x8, None, _Z(6, 4), *pw[1:], _Z(1, 27), 1, 1.0)),
+        ("level attention (bf16)", lambda: ops.level_attention_bf16(_handle(x8, _Z(1, 4, 6, 7, 8, dtype=bf)), x8, None, *pw, _Z(1, 27), 1, 1.0)),
+        ("level attention (bf16)", lambda: ops.level_attention_bf16(x8, _handle(x8, _Z(1, 4, 6, 8, 4, dtype=bf)), None, *pw, _Z(1, 27), 1, 1.0)),
+        ("correlation3d", lambda: ops.correlation3d(_Z(4, 6, 8, 8), _Z(4, 6, 8, 8))),
+        ("warp", lambda: ops.warp(_Z(4, 6, 8, 8), _Z(4, 6, 8, 3))),
+        ("warp", lambda: ops.warp_tee(_Z(4, 6, 8, 8), _Z(4, 6, 8, 3))),
+        ("upsample2", lambda: ops.upsample2(_Z(4, 6, 8, 8))),
+        ("jacdet_nonpos_count", lambda: ops.jacdet_nonpos_count(_Z(4, 6, 8, 3))),
+        ("adam_amsgrad_step_", lambda: ops.adam_amsgrad_step_(_Z(100), _Z(100), _Z(99), _Z(100), _Z(100), 1e-3, 1)),
+        ("adam_amsgrad_step_", lambda: ops.adam_amsgrad_step_(_Z(100), _Z(100), _Z(100), _Z(99), _Z(100), 1e-3, 1)),
+        ("adam_amsgrad_step_", lambda: ops.adam_amsgrad_step_(_Z(100), _Z(100), _Z(100), _Z(100), _Z(99), 1e-3, 1)),
+        ("conv3d_bf16", lambda: ops.conv3d_bf16_forward(_Z(4, 6, 8, 8), w88, b8)),
+        ("conv3d_bf16_backward_data", lambda: ops.conv3d_bf16_backward_data(_Z(4, 6, 8, 8, dtype=bf), w88, 8, True)),
+        ("conv3d_bf16_backward_weight", lambda: ops.conv3d_bf16_backward_weight(_Z(4, 6, 8, 8), _Z(4, 6, 8, 8, dtype=bf))),
+        ("instnorm bf16", lambda: ops._InstNormLReLUBF16PoolSplit.apply(_Z(2, 4, 6, 8, 8, dtype=bf), None, 1e-5, 1)),        # no statistics
+        ("instnorm bf16", lambda: ops._InstNormLReLUBF16PoolSplit.apply(_Z(2, 4, 6, 8, 8, dtype=bf), _Z(64), 1e-5, 2)),      # split outside
+        ("instnorm bf16", lambda: ops._InstNormLReLUBF16PoolSplit.apply(_Z(4, 6, 8, 8, dtype=bf), _Z(64), 1e-5, 1)),         # 4-D
+        ("smilecode_amd", lambda: ops._InstNormLReLUBF16PoolSplit.apply(_Z(2, 4, 6, 8, 8, dtype=bf), _Z(64).cpu(), 1e-5, 1)),
+        ("smilecode_amd", lambda: ops._InstNormLReLUBF16.apply(_Z(1, 4, 6, 8, 8, dtype=bf), _Z(64).cpu(), 1e-5, True)),
+        ("modet_bw", lambda: fn.modet_bw(_Z(1, 4, 5, 6, 27), _Z(1, 4, 5, 6, 6), _Z(1, 6, 7, 8, 6), True)),                 # 5-D query
+        ("kernel size", lambda: fn.modet_fw(q6, k6, _Z(27))),                                                             # a flat rpb
+        # (the device comparisons of functional.modet_fw / modet_bw -- key, rpb, d_attn against query -- need two GPUs: a host
+        #  tensor is refused by _check_input first; label_warp_counts' device rows above are the one-GPU form of that check)
+        # ---- checks that were there already
+        ("smilecode_amd", lambda: ops.instnorm_lrelu(torch.zeros(1, 4, 4, 4, 8))),                                         # CPU tensor: no fallback
+        ("smilecode_amd", lambda: ops.avgpool2(_Z(1, 4, 4, 4, 8, dtype=torch.float64))),
+        ("smilecode_amd", lambda: ops.upsample2(_Z(1, 4, 4, 4, 8).transpose(1, 2))),
+        ("conv3d", lambda: ops.conv3d(x8, _Z(8, 4, 3, 3, 3), b8)),
+        ("warp", lambda: ops.warp(x8, _Z(1, 4, 6, 8, 2))),
+        ("warp", lambda: ops.warp_tee(x8, _Z(2, 4, 6, 8, 3))),
+        ("correlation3d", lambda: ops.correlation3d(x8, _Z(1, 4, 6, 9, 8))),
+        ("NCC", lambda: ops.ncc_loss(_Z(1, 1, 4, 6, 8), _Z(1, 1, 4, 6, 9))),
+        ("NCC", lambda: losses.NCC_vxm()(_Z(1, 1, 4, 6, 8), _Z(1, 2, 4, 6, 8))),
+        ("NCC", lambda: ops.ncc_value_and_grad(_Z(1, 1, 4, 6, 8), _Z(2, 1, 4, 6, 8))),
+        ("Grad3d", lambda: ops.grad3d_loss(_Z(1, 2, 4, 6, 8))),
+        ("Grad3d", lambda: ops.grad3d_value_and_grad_cl(_Z(1, 3, 4, 6, 8))),
+        ("jacdet_nonpos_count", lambda: ops.jacdet_nonpos_count(_Z(1, 4, 6, 8, 2))),
+        ("label_warp_counts", lambda: ops.label_warp_counts(lab.int(), _Z(1, 4, 6, 8, 3), lab)),
+        ("key must be", lambda: fn.modet_fw(q6, _Z(1, 1, 6, 7, 7, 6))),
+        ("kernel size", lambda: fn.modet_fw(q6, k6, _Z(1, 5, 5, 5))),
+    ]
+
+
+def test_errors_are_loud(ops, monkeypatch):
+    """Mismatched arguments are refused on the host, by name, BEFORE a pointer reaches the library: the library object is
+    replaced by a proxy in refuse mode (tests/guard.py), so a row whose host check is missing fails with the proxy's
+    AssertionError instead of launching a kernel on bad arguments."""
+    from smilecode_amd import _lib
+    from tests import guard
+    px = guard.LibProxy(_lib.load(), refuse=True)
+    monkeypatch.setattr(_lib, "_lib", px)
     x = torch.zeros(1, 4, 4, 4, 8)
     with pytest.raises(RuntimeError):
         ops.instnorm_lrelu(x)                                # CPU tensor: no fallback
     with pytest.raises(RuntimeError):
         ops.neighbourhood_attention(torch.zeros(1, 4, 4, 4, 7, device="cuda"), torch.zeros(1, 4, 4, 4, 7, device="cuda"),
                                     torch.zeros(1, 27, device="cuda"), 1, 1.0)   # head_dim 7 unsupported
+    for name, call in _refusals():
+        with pytest.raises(RuntimeError, match=re.escape(name)):
+            call()
+    with pytest.raises(AssertionError, match="refuse mode"):          # the proxy itself: a good call does not get through either
+        ops.avgpool2(_Z(1, 4, 4, 4, 8))
