@@ -145,12 +145,20 @@ SIGNATURES = {
     "modet_cast_bf16": (I, [P, P, I64, I, P]),
 }
 
+# the similarity-loss family beside the frozen core ABI: mirrors include/modet_hip_losses.h one to one, same library
+LOSS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "modet_hip_losses.h")
+LOSS_SIGNATURES = {
+    "modet_mind_ws_bytes": (SZ, [I, I, I, I, I]),
+    "modet_mind_descriptor": (I, [P, P, P, SZ, I, I, I, I, I, I, P]),
+    "modet_mind_fwd_bwd": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, F, P]),
+}
+
 _lib = None
 
 
-def header_symbols():
-    """Every function name include/modet_hip.h declares (used by the export test)."""
-    txt = open(HEADER_PATH).read()
+def header_symbols(path=None):
+    """Every function name include/modet_hip.h (or the header at ``path``) declares (used by the export tests)."""
+    txt = open(path or HEADER_PATH).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(modet_[a-z0-9_]+)\s*\(", txt)))
 
@@ -165,7 +173,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m smilecode_amd.build` "
             "(the ModeT hot path has no CPU / eager fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()):
         if not hasattr(lib, name) and os.environ.get("MODET_HIP_LIB"):
             continue        # an older build loaded for A/B timing may predate an entry point; the product library may not
         fn = getattr(lib, name)

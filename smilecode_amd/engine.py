@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import ops
-from .losses import Grad3d, NCC_vxm
+from .losses import Grad3d, MIND_loss, NCC_vxm
 from .parallel import FlatParams, broadcast_parameters
 
 
@@ -26,8 +26,10 @@ def poly_lr(epoch, max_epoch=30, init_lr=1e-4, power=0.9):
 
 class Trainer:
     def __init__(self, model, lr=1e-4, max_epoch=30, weights=(1.0, 1.0), betas=(0.9, 0.999), eps=1e-8, group=None,
-                 overlap_allreduce=False):
-        """``overlap_allreduce``: all-reduce the gradients in three buckets while the rest of the backward runs
+                 overlap_allreduce=False, sim=None):
+        """``sim``: the similarity term, called as ``sim(fixed, y_moved)``; None = ``NCC_vxm()`` (the reference's train.py:103),
+        ``losses.MIND_loss()`` for multi-modal pairs, or any module (one the step does not know runs through autograd).
+        ``overlap_allreduce``: all-reduce the gradients in three buckets while the rest of the backward runs
         (BASELINE.json configs[4]).  The backward is cut into THREE AUTOGRAD STAGES at the bucket boundaries
         (parallel.MODET_BUCKETS: per-level heads | encoder levels 3-5 | encoder levels 1-2; cut tensors = the encoder's
         per-level features and the pooled input of level 3): stage k writes bucket k's gradients into the flat buffer, then
@@ -51,7 +53,7 @@ class Trainer:
         self.batch_small_launches = os.environ.get("MODET_STEP_BATCHING", "1") != "0"
         self.seed_backward = SEED_BACKWARD  # False: the step goes through loss(...)[0].backward() (tests compare the two)
         self.lr_last = lr
-        self.sim = NCC_vxm()
+        self.sim = NCC_vxm() if sim is None else sim
         self.reg = Grad3d(penalty="l2")
         self.buckets = None
         if overlap_allreduce:
@@ -71,8 +73,11 @@ class Trainer:
     def _seedable(self):
         """the step's own loss path applies: the reference's two loss terms as the HIP kernels have them (cubic NCC window of
         3 / 5 / 7 / 9 voxels, Grad3d without ``loss_mult``) on a model that hands out its channels-last results"""
-        return (self.seed_backward and type(self.sim) is NCC_vxm and type(self.reg) is Grad3d and self.reg.loss_mult is None
-                and len(set(self.sim._w)) == 1 and self.sim._w[0] in (3, 5, 7, 9) and hasattr(self.model, "forward_cl"))
+        if not (self.seed_backward and type(self.reg) is Grad3d and self.reg.loss_mult is None and hasattr(self.model, "forward_cl")):
+            return False
+        if type(self.sim) is MIND_loss:     # (symmetric in its arguments: the kernel differentiates the second, y_moved)
+            return True
+        return type(self.sim) is NCC_vxm and len(set(self.sim._w)) == 1 and self.sim._w[0] in (3, 5, 7, 9)
 
     def _seeded_loss(self, moving, fixed):
         """``loss`` for the step itself: ((loss, sim, reg) detached, roots, seeds) with ``seeds[i]`` = d loss / d ``roots[i]``
@@ -85,7 +90,10 @@ class Trainer:
         y_cl, flow_cl = self.model.forward_cl(moving, fixed)
         B, D, H, W, _ = y_cl.shape
         w0, w1 = float(self.weights[0]), float(self.weights[1])
-        sim, d_y = ops.ncc_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), self.sim._w[0], w0)
+        if type(self.sim) is MIND_loss:
+            sim, d_y = ops.mind_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), w0)
+        else:
+            sim, d_y = ops.ncc_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), self.sim._w[0], w0)
         reg, d_flow = ops.grad3d_value_and_grad_cl(flow_cl.detach(), self.reg.penalty, w1)
         if w0 != 1.0:
             sim = sim * w0

@@ -1,5 +1,6 @@
 """``NCC_vxm`` and ``Grad3d`` with the reference's class names and call signatures
-(ModeT/losses.py:6-94), computed by the HIP kernels of csrc/losses.hip."""
+(ModeT/losses.py:6-94), computed by the HIP kernels of csrc/losses.hip; ``MIND_loss`` (Baseline methods/RCN/losses.py:333-399)
+by those of csrc/mind.hip."""
 from __future__ import annotations
 
 import torch
@@ -41,3 +42,27 @@ class NCC_vxm(torch.nn.Module):
 
     def forward(self, y_true, y_pred):
         return ops.ncc_loss(y_true.contiguous(), y_pred.contiguous(), self._w)
+
+
+class MIND_loss(torch.nn.Module):
+    """MIND-SSC descriptor distance (reference Baseline methods/RCN/losses.py:333-399): mean((MINDSSC(y_pred) - MINDSSC(y_true))^2)
+    with radius 2 and dilation 2, the similarity for multi-modal pairs.  ``win`` is accepted and unused, as in the reference."""
+
+    def __init__(self, win=None):
+        super().__init__()
+        self.win = win
+
+    @staticmethod
+    def _check(y_pred, y_true):
+        for name, t in (("y_pred", y_pred), ("y_true", y_true)):
+            if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
+                raise RuntimeError(f"MIND_loss: {name} must be a non-empty (B,1,D,H,W) volume, got {tuple(t.shape)}")
+        if y_pred.shape != y_true.shape:
+            raise RuntimeError(f"MIND_loss: y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} differ in shape")
+
+    def MINDSSC(self, img, radius=2, dilation=2):
+        return ops.mind_ssc(img.contiguous(), radius, dilation)
+
+    def forward(self, y_pred, y_true):
+        self._check(y_pred, y_true)
+        return ops.mind_loss(y_pred.contiguous(), y_true.contiguous())

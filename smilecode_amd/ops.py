@@ -1788,6 +1788,85 @@ def grad3d_loss(flow, penalty="l2"):
     return _Grad3d.apply(flow, 1 if penalty == "l1" else 2)
 
 
+# ------------------------------------------------------------------------------------------------ MIND-SSC
+MIND_BYTES_PER_VOXEL = 352.0     # modet_mind_fwd_bwd with a gradient, its own traffic: 2 x (4 + 48) descriptor passes, 96 + 48 pointwise,
+                                 # 48 + 4 + 24 box adjoint, 24 + 4 gather
+
+
+def _mind_args(op, *ts, radius=2, dilation=2):
+    _chk(*ts)
+    for t in ts:
+        if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
+            raise RuntimeError(f"{op}: expects non-empty (B,1,D,H,W) volumes, got {tuple(t.shape)}")
+        _same_shape(op, "second volume", t, ts[0].shape, "first volume")
+    if int(radius) != 2 or int(dilation) != 2:
+        raise RuntimeError(f"{op}: only radius 2 and dilation 2 exist (the reference hard-codes them), got {radius} and {dilation}")
+
+
+def mind_ssc(img, radius=2, dilation=2):
+    """the MIND-SSC descriptor (B,12,D,H,W) of a (B,1,D,H,W) image in the reference's channel order.
+    reference: Baseline methods/RCN/losses.py:350-396 (MIND_loss.MINDSSC)"""
+    _mind_args("mind_ssc", img, radius=radius, dilation=dilation)
+    B, _, D, H, W = img.shape
+    out = torch.empty((B, 12, D, H, W), dtype=torch.float32, device=img.device)
+    L = _L()
+    nb = L.modet_mind_ws_bytes(B, D, H, W, 1)
+    if nb == 0:
+        raise RuntimeError(f"mind_ssc: volume {tuple(img.shape)} is out of the kernels' range")
+    ws = _ws(nb, img)
+    nv = float(img.numel())
+    with _Guard(img, "mind_descriptor", 600.0 * nv, 148.0 * nv):
+        _lib.check(L.modet_mind_descriptor(_p(img), _p(out), _p(ws), nb, B, D, H, W, 2, 2, _stream()), "modet_mind_descriptor")
+    return out
+
+
+def _mind_launch(a, b, want_grad, grad_scale=1.0):
+    """modet_mind_fwd_bwd(a, b): (loss (1,), grad_scale * d loss / d b or None)"""
+    B, _, D, H, W = a.shape
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    d_b = torch.empty_like(b) if want_grad else None
+    L = _L()
+    nb = L.modet_mind_ws_bytes(B, D, H, W, 2)
+    if nb == 0:
+        raise RuntimeError(f"MIND: volume {tuple(a.shape)} is out of the kernels' range")
+    ws = _ws(nb, a)
+    nv = float(a.numel())
+    with _Guard(a, "mind_fwd_bwd", 1500.0 * nv, (MIND_BYTES_PER_VOXEL if want_grad else 200.0) * nv):
+        _lib.check(L.modet_mind_fwd_bwd(_p(a), _p(b), _p(loss), _p(d_b), _p(ws), nb, B, D, H, W, 2, 2, float(grad_scale), _stream()),
+                   "modet_mind_fwd_bwd")
+    return loss, d_b
+
+
+class _MIND(Function):
+    """the loss is symmetric in its two arguments, so the gradient w.r.t. the first is the kernel's d_b with the roles swapped
+    (as _NCC).  The value of the swapped call is the same sum in the same order: whichever call ran gives the loss."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        _mind_args("MIND", a, b)
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        d_a = d_b = None
+        if need_a and not need_b:
+            loss, d_a = _mind_launch(b, a, True)
+        else:
+            loss, d_b = _mind_launch(a, b, need_b)
+            if need_a:
+                _, d_a = _mind_launch(b, a, True)
+        ctx.save_for_backward(d_a, d_b)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        d_a, d_b = ctx.saved_tensors
+        g = g.contiguous().reshape(1)
+        return (None if d_a is None else _scale_by(d_a, g)), (None if d_b is None else _scale_by(d_b, g))
+
+
+def mind_loss(a, b):
+    """mean((MIND-SSC(a) - MIND-SSC(b))^2) of two (B,1,D,H,W) volumes.  reference: Baseline methods/RCN/losses.py:398-399"""
+    return _MIND.apply(a, b)
+
+
 # ------------------------------------------------------------------------------------------------ non-autograd
 def ncc_value_and_grad(y_true, y_pred, win=9, grad_scale=1.0):
     """(NCC_vxm(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call -- no autograd node: the
@@ -1807,6 +1886,14 @@ def ncc_value_and_grad(y_true, y_pred, win=9, grad_scale=1.0):
         _lib.check(L.modet_ncc_fwd_bwd_win_scaled(_p(y_true), _p(y_pred), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, int(win),
                                                   float(grad_scale), _stream()), "modet_ncc_fwd_bwd_win_scaled")
     return loss.reshape(()), dJ
+
+
+def mind_value_and_grad(a, b, grad_scale=1.0):
+    """(mind_loss(a, b) as a device scalar, grad_scale * d loss / d b) from one call -- no autograd node: the trainer seeds its
+    backward with the gradient (engine.Trainer._seeded_loss)"""
+    _mind_args("MIND", a, b)
+    loss, d_b = _mind_launch(a, b, True, grad_scale)
+    return loss.reshape(()), d_b
 
 
 def grad3d_value_and_grad_cl(flow_cl, penalty="l2", grad_scale=1.0):

@@ -19,6 +19,7 @@ import torch
 
 from . import data, utils
 from .engine import Trainer, poly_lr
+from .losses import MIND_loss
 from .models import ModeT
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
@@ -87,6 +88,8 @@ def main(argv=None):
                     help="multi-GPU: all-reduce the gradients in three buckets beside the backward (three hipGraph segments)")
     ap.add_argument("--host-loader", action="store_true",
                     help="read the .pkl pair from the host every iteration instead of caching all subjects in HBM")
+    ap.add_argument("--sim", choices=("ncc", "mind"), default="ncc",
+                    help="similarity term: NCC_vxm (mono-modal, the reference's train.py) or the MIND-SSC distance MIND_loss (multi-modal pairs)")
     args = ap.parse_args(argv)
     same_seeds(24)
     rank, local, world = init_from_env()
@@ -95,8 +98,8 @@ def main(argv=None):
     weights = [1, 1]
     head_dim, num_heads = 6, [8, 4, 2, 1, 1]
     img_size = tuple(int(s) for s in args.img_size.split(","))
-    save_dir = "modet-heads({}{}{}{}{})-rpe_headim_{}_ncc_{}_reg_{}_lr_{}_54r/".format(*num_heads, head_dim, weights[0],
-                                                                                       weights[1], args.lr)
+    save_dir = "modet-heads({}{}{}{}{})-rpe_headim_{}_{}_{}_reg_{}_lr_{}_54r/".format(*num_heads, head_dim, args.sim, weights[0],
+                                                                                      weights[1], args.lr)
     exp_dir, log_dir = os.path.join(args.out, "experiments/" + save_dir), os.path.join(args.out, "logs/" + save_dir)
     f = None
     if rank == 0:
@@ -117,7 +120,7 @@ def main(argv=None):
         if rank == 0:
             print(ck)
     trainer = Trainer(model, lr=args.lr, max_epoch=args.max_epoch, weights=weights,   # Adam(amsgrad) + NCC + Grad3d('l2')
-                      overlap_allreduce=args.overlap_allreduce)
+                      overlap_allreduce=args.overlap_allreduce, sim=MIND_loss() if args.sim == "mind" else None)
     if resume is not None and not args.no_restore_optimizer and isinstance(resume.get("optimizer"), dict) \
             and "state" in resume["optimizer"]:
         # the reference saves optimizer.state_dict() but never loads it back (train.py:80-85): a resumed run restarts
