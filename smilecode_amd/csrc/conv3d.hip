@@ -12,6 +12,7 @@
 //   workspace and is summed in fixed order in fp64 (deterministic, no atomics).
 #include "common.h"
 #include "step_ctx.h"
+#include "conv3d_internal.h"
 #include <cstdlib>
 #include <mutex>
 #include <new>
@@ -1581,8 +1582,16 @@ static bool use_direct(int B, int D, int H, int W, int Cin, int Cout) {
   return on && BV <= 16384 && Cin >= 8 && Cin % 4 == 0 && Cout >= 4;
 }
 
-static void conv_direct_launch(const float* x, const float* wpk, const float* bias, float* y, int B, int D, int H, int W,
-                               int Cin, int Cout, hipStream_t s) {
+// the direct kernel (family 3): plain launches only -- no statistics, no normalised input, no activation
+int conv_direct(modet_step_ctx* step, const float* x, const float* w, const float* bias, float* y, float* ws, int B, int D,
+                int H, int W, int Cin, int Cout, int pack_mode, hipStream_t s) {
+  const int CinP = round_up(Cin, 16), CoutP = round_up(Cout, 16), total = 27 * CinP * CoutP;
+  const float* wpk = prepacked_or_record(step, PackKey{w, Cin, Cout, CinP, CoutP, pack_mode + 2, 1});
+  if (!wpk) {
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(cdiv(total, 256) > 1024 ? 1024 : cdiv(total, 256)), dim3(256), 0, s, w,
+                       ws, Cin, Cout, CinP, CoutP, pack_mode + 2, 1);
+    wpk = ws;
+  }
   const int BV = B * D * H * W;
   const int CS = round_up(Cin, 16) / 16, CT = round_up(Cout, 16) / 16;
   const int VT = cdiv(BV, 16);
@@ -1600,24 +1609,15 @@ static void conv_direct_launch(const float* x, const float* wpk, const float* bi
   if (nt2) DIRECT_U(2); else DIRECT_U(1);
 #undef DIRECT_U
 #undef DIRECT_LAUNCH
+  return modet_launch_status();
 }
 
-// query_gx != null: only report the persistent grid's x size (the statistics layout depends on it), launch nothing
+// the exact-f32 tiles (family 0).  query_gx != null: only report the persistent grid's x size (the statistics layout depends
+// on it), launch nothing
 int conv_launch(modet_step_ctx* step, const float* x, const float* w, const float* bias, float* y, float* wpk, int B, int D,
                 int H, int W, int Cin, int Cout, int act, int pack_mode, hipStream_t s, float* stats = nullptr,
                 int* query_gx = nullptr, ConvIn inorm = ConvIn{nullptr, nullptr, 0, nullptr}, bool query_xf = false,
                 bool query_st = false) {
-  if (!query_gx && !stats && !inorm.mean && !act && use_direct(B, D, H, W, Cin, Cout)) {
-    const int CinP = round_up(Cin, 16), CoutP = round_up(Cout, 16), total = 27 * CinP * CoutP;
-    const float* pre = prepacked_or_record(step, PackKey{w, Cin, Cout, CinP, CoutP, pack_mode + 2, 1});
-    if (pre)
-      wpk = const_cast<float*>(pre);
-    else
-      hipLaunchKernelGGL(pack_weights_kernel, dim3(cdiv(total, 256) > 1024 ? 1024 : cdiv(total, 256)), dim3(256), 0, s, w,
-                         wpk, Cin, Cout, CinP, CoutP, pack_mode + 2, 1);
-    conv_direct_launch(x, wpk, bias, y, B, D, H, W, Cin, Cout, s);
-    return modet_launch_status();
-  }
   const FwdPlan p = plan_fwd((int64_t)B * D * H * W, Cin, Cout);
   const int CinP = round_up(Cin, p.ck), CoutP = round_up(Cout, p.ncb);
   const int total = 9 * (p.P + 2) * CinP * CoutP;
@@ -1745,89 +1745,54 @@ inline WgPlan plan_wgrad(int B, int D, int H, int W, int Cin, int Cout) {
 
 }  // namespace
 
-// fp32 emulation on the bf16 matrix pipe (conv3d_bf16.hip, "bf16x3"): fp32 tensors, six exact bf16 piece products per
-// multiply, error <= 3 * 2^-24 |a b| -- the accuracy class of an fp32 FMA at 2.7x less matrix-pipe time.  OPT-IN
-// (MODET_CONV_SPLIT=1) for every eligible shape (Cin % 4 == 0, Cin > 1, Cout % 4 == 0, no fused activation): all parity
-// tests pass with it, but as measured in round 2 (profiles/r02d_split_vs_exact.txt) it wins 1.2-1.4x only at pyramid levels
-// 2-3, ties at level 1 (those kernels are bound by staging the fp32 tile, not by the matrix pipe) and loses at levels
-// 4-5, so the train step does not move (12.37 vs 12.46 ms) and the default stays the exact-f32 MFMA kernels of this file.
-size_t modetx_bf16_prepack_bytes(modet_step_ctx* c);
-void modetx_bf16_prepack_begin(modet_step_ctx* c, void* arena, hipStream_t stream);
-void modetx_bf16_defer_flush(modet_step_ctx* c, hipStream_t stream);
-bool modetx_split_eligible(int Cin, int Cout);
-size_t modetx_split_ws_bytes(int Cin, int Cout);
-size_t modetx_split_stats_bytes(int B, int D, int H, int W, int Cin, int Cout);
-int modetx_split_conv(modet_step_ctx* step, const float* x, const float* w, const float* bias, float* y, void* ws, float* stats,
-                      int B, int D, int H, int W, int Cin, int Cout, int mode, hipStream_t s);
-// bf16x3 z-marching kernels of the few-channel full-resolution layers (conv3d_x3.hip): the default for the shapes they
-// cover; MODET_CONV_X3=0 selects the exact-f32 MFMA kernels of this file for every shape (A/B switch)
-bool modetx_x3_eligible(int B, int D, int H, int W, int Cin, int Cout);
-size_t modetx_x3_ws_bytes(int Cin, int Cout);
-size_t modetx_x3_stats_bytes(int B, int D, int H, int W, int Cin, int Cout);
-int modetx_x3_conv(modet_step_ctx* step, const float* x, const float* w, const float* bias, float* y, void* ws, float* stats,
-                   const float* in_mean, const float* in_rstd, int B, int D, int H, int W, int Cin, int Cout, int act, int mode,
-                   hipStream_t s, const float* amax = nullptr, bool x_free = false);
-size_t modetx_x3_bst_rows_bytes(int B, int D, int H, int W, int Cin, int Cout);
-int modetx_x3_dgrad_bst(modet_step_ctx* step, const float* dy, const float* w, float* dx, const float* xraw, const float* mean,
-                        const float* rstd, float* rows, void* ws, int B, int D, int H, int W, int Cin, int Cout, hipStream_t s,
-                        const float* amax = nullptr);
-bool modetx_x3_wgrad_eligible(int B, int D, int H, int W, int Cin, int Cout);
-size_t modetx_x3_wgrad_ws_bytes(int B, int D, int H, int W, int Cin, int Cout);
-int modetx_x3_wgrad(modet_step_ctx* defer, const float* x, const float* dy, float* dw, float* db, void* ws, int B, int D, int H,
-                    int W, int Cin, int Cout, hipStream_t s, const float* amax = nullptr, const float* in_mean = nullptr,
-                    const float* in_rstd = nullptr);
-// bf16x3 weight gradient through LDS transpose reads (conv3d_wtr.hip): every layer the z-march kernel does not take
-// (Cin >= 12, and the few-channel layers below its voxel threshold); MODET_CONV_WTR=0 restores the exact-f32 kernels (A/B switch)
-bool modetx_wtr_eligible(int B, int D, int H, int W, int Cin, int Cout);
-size_t modetx_wtr_ws_bytes(int B, int D, int H, int W, int Cin, int Cout);
-bool modetx_wtr_batches(int B, int D, int H, int W);
-void modetx_wtr_flush(modet_step_ctx* c, hipStream_t s);
-int modetx_wtr_wgrad(modet_step_ctx* defer, const float* x, const float* dy, float* dw, float* db, void* ws, int B, int D, int H,
-                     int W, int Cin, int Cout, hipStream_t s, const float* amax = nullptr);
-static bool use_x3(int B, int D, int H, int W, int Cin, int Cout) {
-  static const bool on = modet_tuning_env("MODET_CONV_X3") != '0';
-  return on && modetx_x3_eligible(B, D, H, W, Cin, Cout);
-}
-static bool use_x3_wgrad(int B, int D, int H, int W, int Cin, int Cout) {
-  static const bool on = modet_tuning_env("MODET_CONV_X3") != '0';
-  static const bool wtr_first = modet_tuning_env("MODET_CONV_WTR") == '2';      // experiment: the transpose-read kernel everywhere
-  // Cout = 16 (8 -> 16 at level 2) runs 1.7x faster on the transpose-read kernel (102 -> 60 us): the march keeps Cout <= 8
-  return on && !wtr_first && Cout <= 8 && modetx_x3_wgrad_eligible(B, D, H, W, Cin, Cout);
-}
-// bf16x3 forward / data gradient with the K index packed in channel quads (conv3d_q.hip): everything the z-march kernel does
-// not take -- pyramid levels 3-5, the CWM layers, odd channel counts, launches with a lazily normalised input -- up to 1.5 M
-// voxels; MODET_CONV_Q=0 (tuning builds) restores the tiled bf16x3 / exact-f32 / direct kernels
-bool modetx_q_eligible(int B, int D, int H, int W, int Cin, int Cout);
-size_t modetx_q_ws_bytes(int Cin, int Cout);
-size_t modetx_q_stats_bytes(int B, int D, int H, int W, int Cin, int Cout);
-int modetx_q_conv(modet_step_ctx* step, const float* x, const float* w, const float* bias, float* y, void* ws, float* stats,
-                  const float* in_mean, const float* in_rstd, int B, int D, int H, int W, int Cin, int Cout, int mode,
-                  hipStream_t s, const float* amax = nullptr, const float* xraw = nullptr, const float* bmean = nullptr,
-                  const float* brstd = nullptr, float* bst_rows = nullptr, bool x_free = false);
-size_t modetx_q_bst_rows_bytes(int B, int D, int H, int W, int Cin, int Cout);
-static bool use_q(int B, int D, int H, int W, int Cin, int Cout) {
-  static const bool on = modet_tuning_env("MODET_CONV_Q") != '0';
-  // (level 5 -- 2.4 k voxels, 64 / 128 channels -- stays on conv_direct_kernel: 8 stagings of a 128-voxel tile in a row there,
-  // 40-62 us against 40-55; the CWM layers at level-4 resolution, 9.6 k voxels, are faster here: 24->48 35 -> 26 us, 48->48 41 -> 33)
-  const int64_t n = (int64_t)B * D * H * W;
-  // (up to 6 M voxels: at cfg 5's shape -- 160x192x224, two pairs per GPU -- the CWM layers of level 3 run at 1.72 M voxels; with
-  // the round-4 limit of 1.5 M they fell back to the exact-f32 kernels there, 0.42 ms of its 15 ms step)
-  return on && Cin > 1 && !use_x3(B, D, H, W, Cin, Cout) && !(n < 4096 && use_direct(B, D, H, W, Cin, Cout)) && n <= 6000000 &&
-         modetx_q_eligible(B, D, H, W, Cin, Cout);
-}
-static bool use_wtr_wgrad(int B, int D, int H, int W, int Cin, int Cout) {
-  static const bool on = modet_tuning_env("MODET_CONV_WTR") != '0';
-  return on && !use_x3_wgrad(B, D, H, W, Cin, Cout) && modetx_wtr_eligible(B, D, H, W, Cin, Cout);
-}
-// The tiled bf16x3 kernels of conv3d_bf16.hip (SP = 3): default for the MID levels of the pyramid -- Cin >= 16 channels at
-// 16 k .. 1 M voxels (levels 3-4: 16->32 / 32->32 forward 0.077 / 0.131 -> 0.054 / 0.086 ms, 64->64 0.080 -> 0.067); the
-// few-channel full-resolution layers take conv3d_x3.hip, level 5 (2.4 k voxels) stays on the exact-f32 kernels.
-// MODET_CONV_SPLIT=1 forces them for every eligible shape, =0 switches them off.
-static bool use_split(int Cin, int Cout, int64_t nvox = -1) {
+// ---- Which kernel family runs an fp32 convolution (the values: include/modet_hip.h, modet_conv3d_kernel_family_v).  The policy
+// is written ONCE, in route_conv and route_wgrad: every launching entry point, every size / capability query and the report take
+// the family from them, so a buffer is sized for the kernel that runs.  (The families' interfaces: conv3d_internal.h.)
+// EXACT: the exact-f32 MFMA kernels of this file; DIRECT: its conv_direct_kernel (small volumes, plain launches only); the bf16x3
+// families: SPLIT tiled (conv3d_bf16.hip), X3 z-march (conv3d_x3.hip), WTR transpose-read weight gradient (conv3d_wtr.hip), Q channel quads (conv3d_q.hip)
+enum ConvFamily { FAM_EXACT = 0, FAM_SPLIT = 1, FAM_X3 = 2, FAM_DIRECT = 3, FAM_WTR = 4, FAM_Q = 5 };
+enum ConvVariant { CONV_PLAIN = 0, CONV_ACT = 1, CONV_NORMIN = 2, CONV_STATS = 3 };      // what a forward / data-gradient launch fuses
+
+// The A/B switches below (MODET_CONV_*) exist in tuning builds only: the product library reads no environment variable.
+// tiled bf16x3: default for the MID levels of the pyramid -- Cin >= 16 channels at 16 k .. 1 M voxels (levels 3-4: 16->32 /
+// 32->32 forward 0.077 / 0.131 -> 0.054 / 0.086 ms, 64->64 0.080 -> 0.067).  It wins 1.2-1.4x only there
+// (profiles/r02d_split_vs_exact.txt): at level 1 the kernels are bound by staging the fp32 tile, not by the matrix pipe.
+// MODET_CONV_SPLIT=1 forces it for every eligible shape, =0 switches it off.
+static bool use_split(int Cin, int Cout, int64_t nvox) {
   static const int mode = [] { const char e = modet_tuning_env("MODET_CONV_SPLIT"); return e ? (e == '1' ? 1 : 0) : -1; }();
   if (!modetx_split_eligible(Cin, Cout) || mode == 0) return false;
   if (mode == 1) return true;
   return nvox >= 16000 && Cin >= 16 && Cin % 16 == 0 && Cout >= 16;
+}
+static bool conv_x3_on() { static const bool on = modet_tuning_env("MODET_CONV_X3") != '0'; return on; }      // one switch, both routes
+
+// A convolution AS CONVOLVED: the data gradient convolves d_y, so it passes (Cout, Cin) of its layer.
+static ConvFamily route_conv(int B, int D, int H, int W, int Cin, int Cout, int variant) {
+  static const bool q_on = modet_tuning_env("MODET_CONV_Q") != '0';
+  const int64_t n = (int64_t)B * D * H * W;
+  // z-march: the few-channel full-resolution layers, whatever the launch fuses
+  if (conv_x3_on() && modetx_x3_eligible(B, D, H, W, Cin, Cout)) return FAM_X3;
+  // channel quads: everything the z-march kernel does not take -- pyramid levels 3-5, the CWM layers, odd channel counts, launches
+  // with a lazily normalised input -- but for a fused activation (it only occurs in the 1 -> 4 ConvBlock), and:
+  // (level 5 -- 2.4 k voxels, 64 / 128 channels -- stays on conv_direct_kernel: 8 stagings of a 128-voxel tile in a row on quads,
+  // 40-62 us against 40-55; the CWM layers at level-4 resolution, 9.6 k voxels, are faster on quads: 24->48 35 -> 26 us, 48->48 41 -> 33)
+  // (up to 6 M voxels: at cfg 5's shape -- 160x192x224, two pairs per GPU -- the CWM layers of level 3 run at 1.72 M voxels; with
+  // the round-4 limit of 1.5 M they fell back to the exact-f32 kernels there, 0.42 ms of its 15 ms step)
+  const bool direct = use_direct(B, D, H, W, Cin, Cout);
+  if (q_on && variant != CONV_ACT && Cin > 1 && !(n < 4096 && direct) && n <= 6000000 && modetx_q_eligible(B, D, H, W, Cin, Cout))
+    return FAM_Q;
+  if (variant == CONV_ACT || variant == CONV_NORMIN) return FAM_EXACT;
+  if (use_split(Cin, Cout, n)) return FAM_SPLIT;
+  return variant != CONV_STATS && direct ? FAM_DIRECT : FAM_EXACT;      // fused statistics: never the direct kernel
+}
+// The weight gradient of a layer.  y_act: LeakyReLU' folded into the d_y load, which only the first block's kernel does.
+static ConvFamily route_wgrad(int B, int D, int H, int W, int Cin, int Cout, bool y_act) {
+  static const char wtr = modet_tuning_env("MODET_CONV_WTR");      // '0': never transpose reads; '2' (experiment): never the march
+  if (y_act || (Cin == 1 && Cout == 4)) return FAM_EXACT;      // first encoder block: conv_c1_wgrad_mfma_kernel
+  // z-march; Cout = 16 (8 -> 16 at level 2) runs 1.7x faster on the transpose-read kernel (102 -> 60 us): the march keeps Cout <= 8
+  if (conv_x3_on() && wtr != '2' && Cout <= 8 && modetx_x3_wgrad_eligible(B, D, H, W, Cin, Cout)) return FAM_X3;
+  // transpose reads: every layer the march does not take (Cin >= 12, and the few-channel layers below its voxel threshold)
+  return wtr != '0' && modetx_wtr_eligible(B, D, H, W, Cin, Cout) ? FAM_WTR : FAM_EXACT;
 }
 
 extern "C" {
@@ -1839,15 +1804,9 @@ int modet_debug_conv_timing(long long* buf) {       // not in the header: tuning
 #endif
 
 int modet_conv3d_kernel_family_v(int B, int D, int H, int W, int Cin, int Cout, int pass, int variant) {
-  if (Cin == 1) return 0;
-  if (pass == 2) return use_x3_wgrad(B, D, H, W, Cin, Cout) ? 2 : (use_wtr_wgrad(B, D, H, W, Cin, Cout) ? 4 : 0);
-  const int ci = pass == 1 ? Cout : Cin, co = pass == 1 ? Cin : Cout;      // the data gradient convolves d_y (Cout channels)
-  if (use_x3(B, D, H, W, ci, co)) return 2;
-  if (variant != 1 && use_q(B, D, H, W, ci, co)) return 5;     // (a fused activation only occurs in the 1 -> 4 ConvBlock)
-  if (variant == 1 || variant == 2) return 0;                  // fused activation / normalised input: exact-f32 tiles otherwise
-  if (use_split(ci, co, (int64_t)B * D * H * W)) return 1;
-  if (variant == 3) return 0;                                  // fused statistics: never the direct kernel
-  return use_direct(B, D, H, W, ci, co) ? 3 : 0;               // 3: conv_direct_kernel (plain forward / dgrad launches only)
+  if (Cin == 1) return FAM_EXACT;      // reported per LAYER: the one-channel layer (the image) has no data gradient in the model
+  if (pass == 2) return route_wgrad(B, D, H, W, Cin, Cout, false);
+  return pass == 1 ? route_conv(B, D, H, W, Cout, Cin, variant) : route_conv(B, D, H, W, Cin, Cout, variant);
 }
 int modet_conv3d_kernel_family(int B, int D, int H, int W, int Cin, int Cout, int pass) {
   return modet_conv3d_kernel_family_v(B, D, H, W, Cin, Cout, pass, 0);
@@ -1938,7 +1897,57 @@ size_t modet_conv3d_ws_bytes(int Cin, int Cout) {
   return a > d ? a : d;
 }
 
-// x_free: nothing is known about the range of x -> the bf16x3 forms (fp32's range) in the families that have an f16 form
+// InstanceNorm statistics are fused into the conv epilogue (staged or direct-store) for every Cout the model
+// normalises (a multiple of 4, at most 128: 2*Cout columns fit the 256-thread finalize)
+static bool conv_stats_ok(int Cin, int Cout) { return Cin != 1 && Cout % 4 == 0 && Cout <= 128; }
+
+// rows per sample of the statistics buffer: the larger persistent grid of the two instantiations (plain / XF)
+static int conv_stats_rows(int B, int D, int H, int W, int Cin, int Cout) {
+  const int a = conv_grid_x(B, D, H, W, Cin, Cout, false), b = conv_grid_x(B, D, H, W, Cin, Cout, true);
+  return a > b ? a : b;
+}
+
+// the optional operands of one forward / data-gradient launch; the defaults: forward, nothing fused, x bounded (the *_bounded form)
+struct ConvOps {
+  modet_step_ctx* step = nullptr;
+  int mode = 0, act = 0;                                      // mode: 0 forward, 1 data gradient (flipped + transposed weights); act: fused LeakyReLU
+  float* stats = nullptr;                                     // fused InstanceNorm statistics: [B][Cout] shift header, then the family's partial rows
+  const float *in_mean = nullptr, *in_rstd = nullptr;         // lazily normalised input: per-(sample, channel) mean / rstd
+  const float* amax = nullptr;                                // max |d_y| of a data gradient -> its f16 form
+  bool x_free = false;                                        // nothing is known about the range of x -> the bf16x3 forms (fp32's range)
+  const float *xraw = nullptr, *bmean = nullptr, *brstd = nullptr;      // InstanceNorm-backward rows of a data gradient: the norm's raw input, mean, rstd
+  float* rows = nullptr;                                      // ... and the rows it writes
+};
+
+// One convolution of family `fam`, as convolved (a data gradient: x = d_y, y = d_x, the layer's channel counts swapped): the
+// family's workspace check, the statistics' shift header where its kernel expects it filled, and the launch
+static int run_conv(ConvFamily fam, const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int B,
+                    int D, int H, int W, int Cin, int Cout, const ConvOps& o, hipStream_t s) {
+  const size_t need = fam == FAM_X3 ? modetx_x3_ws_bytes(Cin, Cout) : fam == FAM_Q ? modetx_q_ws_bytes(Cin, Cout)
+                    : fam == FAM_SPLIT ? modetx_split_ws_bytes(Cin, Cout) : 0;      // (exact / direct: fwd_ws_elems, checked by every caller)
+  if (ws_bytes < need) return MODET_ERR_WORKSPACE;
+  if (o.stats && (fam == FAM_X3 || fam == FAM_Q))
+    hipLaunchKernelGGL(conv_shift_kernel, dim3(cdiv(B * Cout, 4)), dim3(256), 0, s, x, w, bias, o.in_mean, o.in_rstd, o.stats, B, D,
+                       H, W, Cin, Cout);
+  switch (fam) {
+    case FAM_X3:
+      if (o.rows)      // (this one takes the LAYER's channel counts)
+        return modetx_x3_dgrad_bst(o.step, x, w, y, o.xraw, o.bmean, o.brstd, o.rows, ws, B, D, H, W, Cout, Cin, s, o.amax);
+      return modetx_x3_conv(o.step, x, w, bias, y, ws, o.stats, o.in_mean, o.in_rstd, B, D, H, W, Cin, Cout, o.act, o.mode, s, o.amax,
+                            o.x_free);
+    case FAM_Q:
+      return modetx_q_conv(o.step, x, w, bias, y, ws, o.stats, o.in_mean, o.in_rstd, B, D, H, W, Cin, Cout, o.mode, s, o.amax, o.xraw,
+                           o.bmean, o.brstd, o.rows, o.x_free);
+    case FAM_SPLIT:
+      return modetx_split_conv(o.step, x, w, bias, y, ws, o.stats, B, D, H, W, Cin, Cout, o.mode, s);
+    case FAM_DIRECT:
+      return conv_direct(o.step, x, w, bias, y, (float*)ws, B, D, H, W, Cin, Cout, o.mode, s);
+    default:
+      return conv_launch(o.step, x, w, bias, y, (float*)ws, B, D, H, W, Cin, Cout, o.act, o.mode, s, o.stats, nullptr,
+                         ConvIn{o.in_mean, o.in_rstd, o.stats ? conv_stats_rows(B, D, H, W, Cin, Cout) : 0, nullptr});
+  }
+}
+
 static int conv3d_fwd_impl(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int B,
                            int D, int H, int W, int Cin, int Cout, int act, modet_stream_t stream, modet_step_ctx_t* step, bool x_free) {
   MODET_CHECK_PTR(x); MODET_CHECK_PTR(w); MODET_CHECK_PTR(y); MODET_CHECK_PTR(ws);
@@ -1962,20 +1971,10 @@ static int conv3d_fwd_impl(const float* x, const float* w, const float* bias, fl
     else hipLaunchKernelGGL(conv_c1_fwd_kernel<8>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, x, w, bias, y, D, H, W, total, act);
     return modet_launch_status();
   }
-  if (use_x3(B, D, H, W, Cin, Cout)) {
-    if (ws_bytes < modetx_x3_ws_bytes(Cin, Cout)) return MODET_ERR_WORKSPACE;
-    return modetx_x3_conv(step, x, w, bias, y, ws, nullptr, nullptr, nullptr, B, D, H, W, Cin, Cout, act, 0, (hipStream_t)stream, nullptr, x_free);
-  }
-  if (!act && use_q(B, D, H, W, Cin, Cout)) {
-    if (ws_bytes < modetx_q_ws_bytes(Cin, Cout)) return MODET_ERR_WORKSPACE;
-    return modetx_q_conv(step, x, w, bias, y, ws, nullptr, nullptr, nullptr, B, D, H, W, Cin, Cout, 0, (hipStream_t)stream, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, x_free);
-  }
-  if (!act && use_split(Cin, Cout, (int64_t)B * D * H * W)) {
-    if (ws_bytes < modetx_split_ws_bytes(Cin, Cout)) return MODET_ERR_WORKSPACE;
-    return modetx_split_conv(step, x, w, bias, y, ws, nullptr, B, D, H, W, Cin, Cout, 0, (hipStream_t)stream);
-  }
-  return conv_launch(step, x, w, bias, y, (float*)ws, B, D, H, W, Cin, Cout, act, 0, (hipStream_t)stream);
+  ConvOps o;
+  o.step = step; o.act = act; o.x_free = x_free;
+  return run_conv(route_conv(B, D, H, W, Cin, Cout, act ? CONV_ACT : CONV_PLAIN), x, w, bias, y, ws, ws_bytes, B, D, H, W, Cin, Cout,
+                  o, (hipStream_t)stream);
 }
 int modet_conv3d_fwd(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int B,
                      int D, int H, int W, int Cin, int Cout, int act, modet_stream_t stream, modet_step_ctx_t* step) {
@@ -1986,31 +1985,23 @@ int modet_conv3d_fwd_bounded(const float* x, const float* w, const float* bias, 
   return conv3d_fwd_impl(x, w, bias, y, ws, ws_bytes, B, D, H, W, Cin, Cout, act, stream, step, false);
 }
 
-// InstanceNorm statistics are fused into the conv epilogue (staged or direct-store) for every Cout the model
-// normalises (a multiple of 4, at most 128: 2*Cout columns fit the 256-thread finalize)
-static bool conv_stats_ok(int Cin, int Cout) { return Cin != 1 && Cout % 4 == 0 && Cout <= 128; }
-
-// rows per sample of the statistics buffer: the larger persistent grid of the two instantiations (plain / XF)
-static int conv_stats_rows(int B, int D, int H, int W, int Cin, int Cout) {
-  const int a = conv_grid_x(B, D, H, W, Cin, Cout, false), b = conv_grid_x(B, D, H, W, Cin, Cout, true);
-  return a > b ? a : b;
+// the statistics buffer of a CONV_STATS / CONV_NORMIN launch: [sample][Cout] shift header, then partial sums of (y - shift),
+// (y - shift)^2 in the layout of the family that runs -- x3: one row per workgroup; q, split: one row per output tile; exact:
+// [sample][workgroup][Cout][2]; reduced by modet_instnorm_lrelu_fwd_stats / modet_instnorm_stats
+static size_t conv_stats_bytes(int B, int D, int H, int W, int Cin, int Cout, ConvVariant variant) {
+  if (!conv_stats_ok(Cin, Cout) || B > 32) return 0;
+  switch (route_conv(B, D, H, W, Cin, Cout, variant)) {
+    case FAM_X3: return modetx_x3_stats_bytes(B, D, H, W, Cin, Cout);
+    case FAM_Q: return modetx_q_stats_bytes(B, D, H, W, Cin, Cout);
+    case FAM_SPLIT: return modetx_split_stats_bytes(B, D, H, W, Cin, Cout);
+    default: return ((size_t)B * Cout + (size_t)B * conv_stats_rows(B, D, H, W, Cin, Cout) * Cout * 2) * sizeof(float);
+  }
 }
-
 size_t modet_conv3d_normin_stats_bytes(int B, int D, int H, int W, int Cin, int Cout) {
-  if (!conv_stats_ok(Cin, Cout) || B > 32) return 0;
-  if (use_x3(B, D, H, W, Cin, Cout)) return modetx_x3_stats_bytes(B, D, H, W, Cin, Cout);
-  if (use_q(B, D, H, W, Cin, Cout)) return modetx_q_stats_bytes(B, D, H, W, Cin, Cout);
-  return ((size_t)B * Cout + (size_t)B * conv_stats_rows(B, D, H, W, Cin, Cout) * Cout * 2) * sizeof(float);
+  return conv_stats_bytes(B, D, H, W, Cin, Cout, CONV_NORMIN);
 }
-
 size_t modet_conv3d_stats_bytes(int B, int D, int H, int W, int Cin, int Cout) {
-  if (!conv_stats_ok(Cin, Cout) || B > 32) return 0;
-  if (use_x3(B, D, H, W, Cin, Cout)) return modetx_x3_stats_bytes(B, D, H, W, Cin, Cout);    // one row per workgroup
-  if (use_q(B, D, H, W, Cin, Cout)) return modetx_q_stats_bytes(B, D, H, W, Cin, Cout);      // one row per output tile
-  if (use_split(Cin, Cout, (int64_t)B * D * H * W)) return modetx_split_stats_bytes(B, D, H, W, Cin, Cout);     // one row per output tile
-  // [sample][Cout] shift header, then [sample][workgroup][Cout][2] partial sums of (y - shift), (y - shift)^2; reduced by
-  // modet_instnorm_lrelu_fwd_stats / modet_instnorm_stats
-  return ((size_t)B * Cout + (size_t)B * conv_stats_rows(B, D, H, W, Cin, Cout) * Cout * 2) * sizeof(float);
+  return conv_stats_bytes(B, D, H, W, Cin, Cout, CONV_STATS);
 }
 
 static int conv3d_fwd_stats_impl(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes,
@@ -2021,25 +2012,9 @@ static int conv3d_fwd_stats_impl(const float* x, const float* w, const float* bi
   if (!conv_stats_ok(Cin, Cout)) return MODET_ERR_UNSUPPORTED;
   if (ws_bytes < fwd_ws_elems(Cin, Cout) * sizeof(float)) return MODET_ERR_WORKSPACE;
   if (stats_bytes < modet_conv3d_stats_bytes(B, D, H, W, Cin, Cout)) return MODET_ERR_WORKSPACE;
-  if (use_x3(B, D, H, W, Cin, Cout)) {
-    if (ws_bytes < modetx_x3_ws_bytes(Cin, Cout)) return MODET_ERR_WORKSPACE;
-    hipLaunchKernelGGL(conv_shift_kernel, dim3(cdiv(B * Cout, 4)), dim3(256), 0, (hipStream_t)stream, x, w, bias,
-                       (const float*)nullptr, (const float*)nullptr, stats, B, D, H, W, Cin, Cout);
-    return modetx_x3_conv(step, x, w, bias, y, ws, stats, nullptr, nullptr, B, D, H, W, Cin, Cout, 0, 0, (hipStream_t)stream, nullptr, x_free);
-  }
-  if (use_q(B, D, H, W, Cin, Cout)) {
-    if (ws_bytes < modetx_q_ws_bytes(Cin, Cout)) return MODET_ERR_WORKSPACE;
-    hipLaunchKernelGGL(conv_shift_kernel, dim3(cdiv(B * Cout, 4)), dim3(256), 0, (hipStream_t)stream, x, w, bias,
-                       (const float*)nullptr, (const float*)nullptr, stats, B, D, H, W, Cin, Cout);
-    return modetx_q_conv(step, x, w, bias, y, ws, stats, nullptr, nullptr, B, D, H, W, Cin, Cout, 0, (hipStream_t)stream, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, x_free);
-  }
-  if (use_split(Cin, Cout, (int64_t)B * D * H * W)) {
-    if (ws_bytes < modetx_split_ws_bytes(Cin, Cout)) return MODET_ERR_WORKSPACE;
-    return modetx_split_conv(step, x, w, bias, y, ws, stats, B, D, H, W, Cin, Cout, 0, (hipStream_t)stream);
-  }
-  return conv_launch(step, x, w, bias, y, (float*)ws, B, D, H, W, Cin, Cout, 0, 0, (hipStream_t)stream, stats, nullptr,
-                     ConvIn{nullptr, nullptr, conv_stats_rows(B, D, H, W, Cin, Cout), nullptr});
+  ConvOps o;
+  o.step = step; o.stats = stats; o.x_free = x_free;
+  return run_conv(route_conv(B, D, H, W, Cin, Cout, CONV_STATS), x, w, bias, y, ws, ws_bytes, B, D, H, W, Cin, Cout, o, (hipStream_t)stream);
 }
 int modet_conv3d_fwd_stats(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes,
                            float* stats, size_t stats_bytes, int B, int D, int H, int W, int Cin, int Cout,
@@ -2064,30 +2039,20 @@ int modet_conv3d_fwd_normin(const float* x_raw, const float* in_mean, const floa
     if (!conv_stats_ok(Cin, Cout)) return MODET_ERR_UNSUPPORTED;
     if (stats_bytes < modet_conv3d_normin_stats_bytes(B, D, H, W, Cin, Cout)) return MODET_ERR_WORKSPACE;
   }
-  if (use_x3(B, D, H, W, Cin, Cout)) {
-    if (ws_bytes < modetx_x3_ws_bytes(Cin, Cout)) return MODET_ERR_WORKSPACE;
-    if (stats)
-      hipLaunchKernelGGL(conv_shift_kernel, dim3(cdiv(B * Cout, 4)), dim3(256), 0, (hipStream_t)stream, x_raw, w, bias, in_mean,
-                         in_rstd, stats, B, D, H, W, Cin, Cout);
-    return modetx_x3_conv(step, x_raw, w, bias, y, ws, stats, in_mean, in_rstd, B, D, H, W, Cin, Cout, 0, 0, (hipStream_t)stream);
-  }
-  if (use_q(B, D, H, W, Cin, Cout)) {
-    if (ws_bytes < modetx_q_ws_bytes(Cin, Cout)) return MODET_ERR_WORKSPACE;
-    if (stats)
-      hipLaunchKernelGGL(conv_shift_kernel, dim3(cdiv(B * Cout, 4)), dim3(256), 0, (hipStream_t)stream, x_raw, w, bias, in_mean,
-                         in_rstd, stats, B, D, H, W, Cin, Cout);
-    return modetx_q_conv(step, x_raw, w, bias, y, ws, stats, in_mean, in_rstd, B, D, H, W, Cin, Cout, 0, (hipStream_t)stream);
-  }
-  return conv_launch(step, x_raw, w, bias, y, (float*)ws, B, D, H, W, Cin, Cout, 0, 0, (hipStream_t)stream, stats, nullptr,
-                     ConvIn{in_mean, in_rstd, stats ? conv_stats_rows(B, D, H, W, Cin, Cout) : 0, nullptr});
+  ConvOps o;
+  o.step = step; o.stats = stats; o.in_mean = in_mean; o.in_rstd = in_rstd;
+  return run_conv(route_conv(B, D, H, W, Cin, Cout, CONV_NORMIN), x_raw, w, bias, y, ws, ws_bytes, B, D, H, W, Cin, Cout, o,
+                  (hipStream_t)stream);
 }
 
 size_t modet_conv3d_bwd_data_instats_bytes(int B, int D, int H, int W, int Cin, int Cout) {
   if (B > 32 || Cin % 4 != 0) return 0;
-  if (use_x3(B, D, H, W, Cout, Cin)) return modetx_x3_bst_rows_bytes(B, D, H, W, Cin, Cout);
-  // the channel-quad kernel (family 5) carries the same epilogue; 2 Cin <= 256: the rows' finalize sums 2 Cin columns
-  if (use_q(B, D, H, W, Cout, Cin) && 2 * Cin <= 256) return modetx_q_bst_rows_bytes(B, D, H, W, Cout, Cin);
-  return 0;
+  // the z-march and the channel-quad kernel carry this epilogue; 2 Cin <= 256: the rows' finalize sums 2 Cin columns
+  switch (route_conv(B, D, H, W, Cout, Cin, CONV_PLAIN)) {
+    case FAM_X3: return modetx_x3_bst_rows_bytes(B, D, H, W, Cin, Cout);
+    case FAM_Q: return 2 * Cin <= 256 ? modetx_q_bst_rows_bytes(B, D, H, W, Cout, Cin) : 0;
+    default: return 0;
+  }
 }
 
 int modet_conv3d_bwd_data_instats(const float* d_y, const float* w, float* d_x, const float* x_raw, const float* mean,
@@ -2107,13 +2072,11 @@ int modet_conv3d_bwd_data_instats_amax(const float* d_y, const float* w, float* 
   const size_t need = modet_conv3d_bwd_data_instats_bytes(B, D, H, W, Cin, Cout);
   if (need == 0) return MODET_ERR_UNSUPPORTED;
   if (rows_bytes < need) return MODET_ERR_WORKSPACE;
-  if (!use_x3(B, D, H, W, Cout, Cin)) {
-    if (ws_bytes < modetx_q_ws_bytes(Cout, Cin)) return MODET_ERR_WORKSPACE;
-    return modetx_q_conv(step, d_y, w, nullptr, d_x, ws, nullptr, nullptr, nullptr, B, D, H, W, Cout, Cin, 1, (hipStream_t)stream,
-                         dy_amax, x_raw, mean, rstd, rows);
-  }
-  if (ws_bytes < fwd_ws_elems(Cout, Cin) * sizeof(float) || ws_bytes < modetx_x3_ws_bytes(Cout, Cin)) return MODET_ERR_WORKSPACE;
-  return modetx_x3_dgrad_bst(step, d_y, w, d_x, x_raw, mean, rstd, rows, ws, B, D, H, W, Cin, Cout, (hipStream_t)stream, dy_amax);
+  const ConvFamily fam = route_conv(B, D, H, W, Cout, Cin, CONV_PLAIN);      // (need != 0: the z-march or the channel quads)
+  if (fam == FAM_X3 && ws_bytes < fwd_ws_elems(Cout, Cin) * sizeof(float)) return MODET_ERR_WORKSPACE;
+  ConvOps o;
+  o.step = step; o.mode = 1; o.amax = dy_amax; o.xraw = x_raw; o.bmean = mean; o.brstd = rstd; o.rows = rows;
+  return run_conv(fam, d_y, w, nullptr, d_x, ws, ws_bytes, B, D, H, W, Cout, Cin, o, (hipStream_t)stream);
 }
 
 int modet_conv3d_bwd_data(const float* d_y, const float* w, float* d_x, void* ws, size_t ws_bytes, int B, int D, int H,
@@ -2127,21 +2090,10 @@ int modet_conv3d_bwd_data_amax(const float* d_y, const float* w, float* d_x, voi
   MODET_CHECK_DIM(B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0);
   if (ws_bytes < fwd_ws_elems(Cout, Cin) * sizeof(float)) return MODET_ERR_WORKSPACE;
   // a convolution of d_y (Cout channels) producing Cin channels
-  if (use_x3(B, D, H, W, Cout, Cin)) {
-    if (ws_bytes < modetx_x3_ws_bytes(Cout, Cin)) return MODET_ERR_WORKSPACE;
-    return modetx_x3_conv(step, d_y, w, nullptr, d_x, ws, nullptr, nullptr, nullptr, B, D, H, W, Cout, Cin, 0, 1, (hipStream_t)stream,
-                          dy_amax);
-  }
-  if (use_q(B, D, H, W, Cout, Cin)) {
-    if (ws_bytes < modetx_q_ws_bytes(Cout, Cin)) return MODET_ERR_WORKSPACE;
-    return modetx_q_conv(step, d_y, w, nullptr, d_x, ws, nullptr, nullptr, nullptr, B, D, H, W, Cout, Cin, 1, (hipStream_t)stream,
-                         dy_amax);
-  }
-  if (use_split(Cout, Cin, (int64_t)B * D * H * W)) {
-    if (ws_bytes < modetx_split_ws_bytes(Cout, Cin)) return MODET_ERR_WORKSPACE;
-    return modetx_split_conv(step, d_y, w, nullptr, d_x, ws, nullptr, B, D, H, W, Cout, Cin, 1, (hipStream_t)stream);
-  }
-  return conv_launch(step, d_y, w, nullptr, d_x, (float*)ws, B, D, H, W, Cout, Cin, 0, 1, (hipStream_t)stream);
+  ConvOps o;
+  o.step = step; o.mode = 1; o.amax = dy_amax;
+  return run_conv(route_conv(B, D, H, W, Cout, Cin, CONV_PLAIN), d_y, w, nullptr, d_x, ws, ws_bytes, B, D, H, W, Cout, Cin, o,
+                  (hipStream_t)stream);
 }
 
 size_t modet_conv3d_bwd_weight_ws_bytes(int B, int D, int H, int W, int Cin, int Cout) {
@@ -2151,20 +2103,11 @@ size_t modet_conv3d_bwd_weight_ws_bytes(int B, int D, int H, int W, int Cin, int
   const size_t fl = (size_t)gx * p.gy * p.ng * 256;
   const size_t c1 = (size_t)C1_MFMA_BLOCKS * 4 * 2 * 256;       // per-wave partial tiles of conv_c1_wgrad_mfma_kernel
   size_t n = (fl > c1 ? fl : c1) * sizeof(float);
-  if (use_x3_wgrad(B, D, H, W, Cin, Cout)) {
-    const size_t x3 = modetx_x3_wgrad_ws_bytes(B, D, H, W, Cin, Cout);
-    n = n > x3 ? n : x3;
-  }
-  if (use_wtr_wgrad(B, D, H, W, Cin, Cout)) {
-    const size_t w3 = modetx_wtr_ws_bytes(B, D, H, W, Cin, Cout);
-    n = n > w3 ? n : w3;
-  }
-  return n;
+  const ConvFamily fam = route_wgrad(B, D, H, W, Cin, Cout, false);
+  const size_t b16 = fam == FAM_X3 ? modetx_x3_wgrad_ws_bytes(B, D, H, W, Cin, Cout)
+                   : fam == FAM_WTR ? modetx_wtr_ws_bytes(B, D, H, W, Cin, Cout) : 0;
+  return n > b16 ? n : b16;
 }
-
-static int conv_bwd_weight_impl(const float* x, const float* d_y, const float* y_act, float* d_w, float* d_bias, void* ws,
-                                size_t ws_bytes, int B, int D, int H, int W, int Cin, int Cout, modet_stream_t stream,
-                                modet_step_ctx* defer = nullptr, const float* dy_amax = nullptr);
 
 // ---- deferred reductions: modet_conv3d_bwd_weight*_defer only produce the partial tiles (the workspace must stay
 // untouched until the flush) and queue the reduction in the caller's step context; modet_conv3d_wgrad_defer_flush runs
@@ -2185,8 +2128,51 @@ static void reduce_or_defer(const ReduceJob& j, int blocks, hipStream_t s, modet
                        j.n_ci, j.cit, j.ng);
 }
 
+static int conv_bwd_weight_impl(const float* x, const float* d_y, const float* y_act, float* d_w, float* d_bias, void* ws,
+                                size_t ws_bytes, int B, int D, int H, int W, int Cin, int Cout, modet_stream_t stream,
+                                modet_step_ctx* defer = nullptr, const float* dy_amax = nullptr) {
+  MODET_CHECK_PTR(x); MODET_CHECK_PTR(d_y); MODET_CHECK_PTR(d_w); MODET_CHECK_PTR(ws);
+  MODET_CHECK_DIM(B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0);
+  if (Cout > NTHR) return MODET_ERR_UNSUPPORTED;
+  if (ws_bytes < modet_conv3d_bwd_weight_ws_bytes(B, D, H, W, Cin, Cout)) return MODET_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const ConvFamily fam = route_wgrad(B, D, H, W, Cin, Cout, y_act != nullptr);
+  if (fam == FAM_X3) return modetx_x3_wgrad(defer, x, d_y, d_w, d_bias, ws, B, D, H, W, Cin, Cout, s, dy_amax);
+  if (fam == FAM_WTR) return modetx_wtr_wgrad(defer, x, d_y, d_w, d_bias, ws, B, D, H, W, Cin, Cout, s, dy_amax);
+  if (Cin == 1 && Cout == 4) {
+    const int tx = cdiv(W, TX), ty = cdiv(H, WG_TY), tz = cdiv(D, C1_TZ);
+    const int ntiles = B * tx * ty * tz;
+    const int nblk = ntiles < C1_MFMA_BLOCKS ? ntiles : C1_MFMA_BLOCKS;
+    hipLaunchKernelGGL(conv_c1_wgrad_mfma_kernel, dim3(nblk), dim3(NTHR), 0, s, x, d_y, y_act, (float*)ws, D, H, W, tx, ty, tz,
+                       ntiles);
+    reduce_or_defer(ReduceJob{(const float*)ws, d_w, d_bias, 1, 4, nblk, 1, 1, 1, 2, 0}, 2 * 4, s, defer);
+    return modet_launch_status();
+  }
+  const WgPlan p = plan_wgrad(B, D, H, W, Cin, Cout);
+  float* part = (float*)ws;
+  if (p.np) {
+    const bool rowld = Cin == 8 && Cout == 8;
+#define NP_LAUNCH(TZ_, R_) hipLaunchKernelGGL((conv3d_wgrad_np_kernel<8, TZ_, R_>), dim3(p.gx), dim3(NTHR), 0, s, x, d_y, part, D, \
+                                               H, W, Cin, Cout, p.tiles_x, p.tiles_y, p.tiles_z, p.ntiles)
+    if (p.tz == 4) { if (rowld) NP_LAUNCH(4, true); else NP_LAUNCH(4, false); }
+    else { if (rowld) NP_LAUNCH(2, true); else NP_LAUNCH(2, false); }
+#undef NP_LAUNCH
+    reduce_or_defer(ReduceJob{(const float*)part, d_w, d_bias, Cin, Cout, p.gx, 1, 1, p.cit, p.ng, 1}, p.ng * 4, s, defer);
+    return modet_launch_status();
+  }
+  dim3 grid(p.gx, p.gy);
+#define WG_LAUNCH(CIT_, TZ_) hipLaunchKernelGGL((conv3d_wgrad_kernel<CIT_, TZ_>), grid, dim3(NTHR), 0, s, x, d_y, part, D, H, W, \
+                                               Cin, Cout, p.tiles_x, p.tiles_y, p.tiles_z, p.ntiles, p.n_ci)
+  if (p.cit == 4) { if (p.tz == 4) WG_LAUNCH(4, 4); else WG_LAUNCH(4, 2); }
+  else if (p.cit == 8) { if (p.tz == 4) WG_LAUNCH(8, 4); else WG_LAUNCH(8, 2); }
+  else WG_LAUNCH(16, 2);
+#undef WG_LAUNCH
+  reduce_or_defer(ReduceJob{(const float*)part, d_w, d_bias, Cin, Cout, p.gx, p.gy, p.n_ci, p.cit, p.ng, 0}, p.gy * p.ng * 4, s, defer);
+  return modet_launch_status();
+}
+
 int modet_conv3d_wgrad_defers_operands(int B, int D, int H, int W, int Cin, int Cout) {
-  return use_wtr_wgrad(B, D, H, W, Cin, Cout) && modetx_wtr_batches(B, D, H, W) ? 1 : 0;
+  return route_wgrad(B, D, H, W, Cin, Cout, false) == FAM_WTR && modetx_wtr_batches(B, D, H, W) ? 1 : 0;
 }
 
 int modet_conv3d_wgrad_defer_flush(modet_step_ctx_t* c, modet_stream_t stream) {
@@ -2232,7 +2218,7 @@ int modet_conv3d_bwd_weight_amax(const float* x, const float* d_y, float* d_w, f
 }
 
 int modet_conv3d_bwd_weight_normin_ok(int B, int D, int H, int W, int Cin, int Cout) {
-  return use_x3_wgrad(B, D, H, W, Cin, Cout) ? 1 : 0;
+  return route_wgrad(B, D, H, W, Cin, Cout, false) == FAM_X3 ? 1 : 0;
 }
 
 int modet_conv3d_bwd_weight_normin(const float* x_raw, const float* in_mean, const float* in_rstd, const float* d_y, float* d_w,
@@ -2240,7 +2226,7 @@ int modet_conv3d_bwd_weight_normin(const float* x_raw, const float* in_mean, con
                                    const float* dy_amax, modet_stream_t stream, modet_step_ctx_t* step) {
   MODET_CHECK_PTR(x_raw); MODET_CHECK_PTR(in_mean); MODET_CHECK_PTR(in_rstd); MODET_CHECK_PTR(d_y); MODET_CHECK_PTR(d_w); MODET_CHECK_PTR(ws);
   MODET_CHECK_DIM(B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0);
-  if (!use_x3_wgrad(B, D, H, W, Cin, Cout)) return MODET_ERR_UNSUPPORTED;
+  if (route_wgrad(B, D, H, W, Cin, Cout, false) != FAM_X3) return MODET_ERR_UNSUPPORTED;
   if (ws_bytes < modet_conv3d_bwd_weight_ws_bytes(B, D, H, W, Cin, Cout)) return MODET_ERR_WORKSPACE;
   return modetx_x3_wgrad(step, x_raw, d_y, d_w, d_bias, ws, B, D, H, W, Cin, Cout, (hipStream_t)stream, dy_amax, in_mean, in_rstd);
 }
@@ -2251,50 +2237,6 @@ int modet_conv3d_bwd_weight_act(const float* x, const float* d_y, const float* y
   MODET_CHECK_PTR(y_act);
   if (!(Cin == 1 && Cout == 4)) return MODET_ERR_UNSUPPORTED;     // only the first encoder block (ConvBlock 1 -> 4)
   return conv_bwd_weight_impl(x, d_y, y_act, d_w, d_bias, ws, ws_bytes, B, D, H, W, Cin, Cout, stream);
-}
-
-static int conv_bwd_weight_impl(const float* x, const float* d_y, const float* y_act, float* d_w, float* d_bias, void* ws,
-                                size_t ws_bytes, int B, int D, int H, int W, int Cin, int Cout, modet_stream_t stream,
-                                modet_step_ctx* defer, const float* dy_amax) {
-  MODET_CHECK_PTR(x); MODET_CHECK_PTR(d_y); MODET_CHECK_PTR(d_w); MODET_CHECK_PTR(ws);
-  MODET_CHECK_DIM(B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0);
-  if (Cout > NTHR) return MODET_ERR_UNSUPPORTED;
-  if (ws_bytes < modet_conv3d_bwd_weight_ws_bytes(B, D, H, W, Cin, Cout)) return MODET_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  if (Cin == 1 && Cout == 4) {
-    const int tx = cdiv(W, TX), ty = cdiv(H, WG_TY), tz = cdiv(D, C1_TZ);
-    const int ntiles = B * tx * ty * tz;
-    const int nblk = ntiles < C1_MFMA_BLOCKS ? ntiles : C1_MFMA_BLOCKS;
-    hipLaunchKernelGGL(conv_c1_wgrad_mfma_kernel, dim3(nblk), dim3(NTHR), 0, s, x, d_y, y_act, (float*)ws, D, H, W, tx, ty, tz,
-                       ntiles);
-    reduce_or_defer(ReduceJob{(const float*)ws, d_w, d_bias, 1, 4, nblk, 1, 1, 1, 2, 0}, 2 * 4, s, defer);
-    return modet_launch_status();
-  }
-  if (!y_act && use_x3_wgrad(B, D, H, W, Cin, Cout))
-    return modetx_x3_wgrad(defer, x, d_y, d_w, d_bias, ws, B, D, H, W, Cin, Cout, s, dy_amax);
-  if (!y_act && use_wtr_wgrad(B, D, H, W, Cin, Cout))
-    return modetx_wtr_wgrad(defer, x, d_y, d_w, d_bias, ws, B, D, H, W, Cin, Cout, s, dy_amax);
-  const WgPlan p = plan_wgrad(B, D, H, W, Cin, Cout);
-  float* part = (float*)ws;
-  if (p.np) {
-    const bool rowld = Cin == 8 && Cout == 8;
-#define NP_LAUNCH(TZ_, R_) hipLaunchKernelGGL((conv3d_wgrad_np_kernel<8, TZ_, R_>), dim3(p.gx), dim3(NTHR), 0, s, x, d_y, part, D, \
-                                               H, W, Cin, Cout, p.tiles_x, p.tiles_y, p.tiles_z, p.ntiles)
-    if (p.tz == 4) { if (rowld) NP_LAUNCH(4, true); else NP_LAUNCH(4, false); }
-    else { if (rowld) NP_LAUNCH(2, true); else NP_LAUNCH(2, false); }
-#undef NP_LAUNCH
-    reduce_or_defer(ReduceJob{(const float*)part, d_w, d_bias, Cin, Cout, p.gx, 1, 1, p.cit, p.ng, 1}, p.ng * 4, s, defer);
-    return modet_launch_status();
-  }
-  dim3 grid(p.gx, p.gy);
-#define WG_LAUNCH(CIT_, TZ_) hipLaunchKernelGGL((conv3d_wgrad_kernel<CIT_, TZ_>), grid, dim3(NTHR), 0, s, x, d_y, part, D, H, W, \
-                                               Cin, Cout, p.tiles_x, p.tiles_y, p.tiles_z, p.ntiles, p.n_ci)
-  if (p.cit == 4) { if (p.tz == 4) WG_LAUNCH(4, 4); else WG_LAUNCH(4, 2); }
-  else if (p.cit == 8) { if (p.tz == 4) WG_LAUNCH(8, 4); else WG_LAUNCH(8, 2); }
-  else WG_LAUNCH(16, 2);
-#undef WG_LAUNCH
-  reduce_or_defer(ReduceJob{(const float*)part, d_w, d_bias, Cin, Cout, p.gx, p.gy, p.n_ci, p.cit, p.ng, 0}, p.gy * p.ng * 4, s, defer);
-  return modet_launch_status();
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 // dgrad is the same kernel on flipped + transposed weights.
 #include "common.h"
 #include "step_ctx.h"
+#include "conv3d_internal.h"
 #include <mutex>
 #include <vector>
 
@@ -973,15 +974,6 @@ void modetx_bf16_defer_flush(modet_step_ctx* c, hipStream_t stream) {
 }
 
 // ---- 16-bit side of modet_conv3d_prepack_* (conv3d.hip owns the entry points; these jobs follow the fp32 jobs in the arena)
-void modetx_x3_prepack_begin(modet_step_ctx* c, hipStream_t stream);          // conv3d_x3.hip: its jobs have layout >= 2
-bool modetx_x3_bf16_eligible(int B, int D, int H, int W, int Cin, int Cout, int x_bf16);
-int modetx_x3_bf16_rows_per_sample(int B, int D, int H, int W, int Cin, int Cout);
-int modetx_x3_bf16_conv(modet_step_ctx* step, const void* x, int x_bf16, const float* w, const float* bias, void* y, int y_bf16,
-                        void* ws, float* stats, int B, int D, int H, int W, int Cin, int Cout, int mode, hipStream_t s);
-bool modetx_x3_bf16_wgrad_eligible(int B, int D, int H, int W, int Cin, int Cout, int x_bf16);
-size_t modetx_x3_bf16_wgrad_ws_bytes(int B, int D, int H, int W, int Cin, int Cout);
-int modetx_x3_bf16_wgrad(modet_step_ctx* defer, const void* x, int x_bf16, const void* dy, float* dw, float* db, void* ws, int B,
-                         int D, int H, int W, int Cin, int Cout, hipStream_t s);
 size_t modetx_bf16_prepack_bytes(modet_step_ctx* c) {
   std::lock_guard<std::mutex> lk(c->mu);
   size_t n = 0;

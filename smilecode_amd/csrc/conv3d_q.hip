@@ -26,6 +26,7 @@
 // dgrad = the same kernel on flipped / transposed weights (mode 1).
 #include "common.h"
 #include "step_ctx.h"
+#include "conv3d_internal.h"
 #include <mutex>
 #include <vector>
 

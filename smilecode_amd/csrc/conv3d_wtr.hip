@@ -32,6 +32,7 @@
 // workgroups (deterministic).  The bias gradient is one more accumulator (A = ones).
 #include "common.h"
 #include "step_ctx.h"
+#include "conv3d_internal.h"
 
 namespace {
 
@@ -461,8 +462,6 @@ extern "C" int modet_debug_wtr_timing(long long* buf) {       // not in the head
 #endif
 
 // ---- internal interface for conv3d.hip (C++ linkage, not part of the ABI)
-int modetx_wgrad_partials_reduce2(modet_step_ctx* defer, const float* part, float* red, float* dw, float* db, int gx, int gy,
-                                  int Cin, int Cout, int nq, int mt, int nt, int n_coblk, hipStream_t s);      // conv3d_bf16.hip
 bool modetx_wtr_eligible(int B, int D, int H, int W, int Cin, int Cout) {
   const int64_t n = (int64_t)B * D * H * W;
   const bool vec = Cin % 4 == 0 && Cout % 4 == 0;

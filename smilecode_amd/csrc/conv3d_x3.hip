@@ -23,6 +23,7 @@
 // dgrad is the same kernel on flipped / transposed weights.
 #include "common.h"
 #include "step_ctx.h"
+#include "conv3d_internal.h"
 #include <type_traits>
 
 namespace {
@@ -1287,8 +1288,6 @@ int modetx_x3_bf16_conv(modet_step_ctx* step, const void* x, int x_bf16, const f
   return stats ? x3_launch16<false, true, true>(step, a, w, ws, B, mode, p, s) : x3_launch16<false, true, false>(step, a, w, ws, B, mode, p, s);
 }
 // ---- weight gradient
-int modetx_wgrad_partials_reduce(modet_step_ctx* defer, const float* part, float* red, float* dw, float* db, int gx, int Cin,
-                                 int Cout, int cib, int u, int layout, hipStream_t s);      // conv3d_bf16.hip
 bool modetx_x3_wgrad_eligible(int B, int D, int H, int W, int Cin, int Cout) {
   return Cin % 4 == 0 && Cin >= 4 && Cin <= 8 && Cout % 4 == 0 && Cout >= 4 && Cout <= 16 && (int64_t)B * D * H * W >= 200000 &&
          (int64_t)H * W * 16 * 4 < 0x7fffffffLL;
@@ -1348,7 +1347,6 @@ int modetx_x3_bf16_wgrad(modet_step_ctx* defer, const void* x, int x_bf16, const
   return modetx_wgrad_partials_reduce(defer, (const float*)ws, red, dw, db, p.gx, Cin, Cout, p.cib, p.u, p.np ? 1 : 0, s);
 }
 
-void modetx_q_prepack_begin(modet_step_ctx* c, hipStream_t stream);      // conv3d_q.hip: layout 4
 // the recorded 16-bit packing jobs with layout 2 / 3 belong to this file (conv3d_bf16.hip's prepack launch skips layouts >= 2)
 void modetx_x3_prepack_begin(modet_step_ctx* c, hipStream_t stream) {
   std::vector<PackBKey> jobs;

@@ -180,7 +180,10 @@ class trace_range:
 
 
 _FAM_CACHE = {}
-_FAM_SUFFIX = ("", "@split", "@x3", "@direct", "@tr", "@q")
+_FAM_SUFFIX = ("", "@split", "@x3", "@direct", "@tr", "@q")     # by family (include/modet_hip.h, modet_conv3d_kernel_family_v)
+_FAM_BF16X3_FWD = (1, 2, 5)     # forward kernels on bf16 pieces: fused InstanceNorm statistics cost them nothing
+_FAM_F16_DGRAD = (2, 5)         # data-gradient kernels with a two-f16-piece form, which takes max |d_y|
+_FAM_F16_FORM = (2, 4, 5)       # every family with a two-f16-piece form (4: the transpose-read weight gradient)
 
 
 def _conv_tag(kind, x_shape, Cin, Cout, variant=0, f16=None):
@@ -199,7 +202,7 @@ def _conv_tag(kind, x_shape, Cin, Cout, variant=0, f16=None):
         B, D, H, W = x_shape[:4]
         fam = _L().modet_conv3d_kernel_family_v(B, D, H, W, Cin, Cout, {"fwd": 0, "dgrad": 1, "wgrad": 2}[kind], variant)
         arrow = f"{Cout}->{Cin}" if kind == "dgrad" else f"{Cin}->{Cout}"
-        half = f16 and D * H * W < (1 << 24) and fam in (2, 4, 5)
+        half = f16 and D * H * W < (1 << 24) and fam in _FAM_F16_FORM
         t = _FAM_CACHE[key] = f"conv_{kind}[{arrow}]{_FAM_SUFFIX[fam]}" + ("h" if half else "")
     return t
 
@@ -219,6 +222,34 @@ def _conv16_tag(kind, x_shape, Cin, Cout, x_bf16):
 
 
 # ------------------------------------------------------------------------------------------------ raw calls
+def _conv_fwd(x, w, b, step, bounded=False, act=False, norm=None, want_stats=False):
+    """THE forward conv launch (arguments already checked): output, workspace, statistics buffer, tag and the one library call.
+    bounded: x is inside the f16 forms' range; act: fused LeakyReLU; norm = (mean, rstd): x is raw, normalised while staged;
+    want_stats: InstanceNorm partial statistics from the epilogue.  Returns (y, stats or None)."""
+    B, D, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    L = _L()
+    y = torch.empty((B, D, H, W, Cout), dtype=torch.float32, device=x.device)
+    nb = L.modet_conv3d_ws_bytes(Cin, Cout)
+    ws = _ws(nb, x)
+    sb = (L.modet_conv3d_normin_stats_bytes if norm else L.modet_conv3d_stats_bytes)(B, D, H, W, Cin, Cout) if want_stats else 0
+    # (a normalised-input launch goes without statistics where the configuration has none; the statistics launch does not)
+    stats = torch.empty(sb // 4, dtype=torch.float32, device=x.device) if sb > 0 or (want_stats and not norm) else None
+    n = float(B) * D * H * W
+    variant = 2 if norm else (3 if want_stats else int(bool(act)))
+    out, dims = (_p(w), _p(b), _p(y), _p(ws), nb), (B, D, H, W, Cin, Cout)
+    with _Guard(x, _conv_tag("fwd", x.shape, Cin, Cout, variant, f16=bool(bounded or norm)), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
+        if norm:
+            _lib.check(L.modet_conv3d_fwd_normin(_p(x), *map(_p, norm), *out, _p(stats), sb, *dims, _stream(), _h(step)), "modet_conv3d_fwd_normin")
+        elif want_stats:
+            fn = L.modet_conv3d_fwd_stats_bounded if bounded else L.modet_conv3d_fwd_stats
+            _lib.check(fn(_p(x), *out, _p(stats), sb, *dims, _stream(), _h(step)), "modet_conv3d_fwd_stats")
+        else:
+            fn = L.modet_conv3d_fwd_bounded if bounded else L.modet_conv3d_fwd
+            _lib.check(fn(_p(x), *out, *dims, int(act), _stream(), _h(step)), "modet_conv3d_fwd")
+    return y, stats
+
+
 def conv3d_forward(x, w, b, act, step=None, x_act=False):
     """x_act: the caller's word that x is an activation inside the f16 forms' range (include/modet_hip.h, "TWO f16 PIECES":
     |x| < 4 094) -> the *_bounded entry point, half the matrix work; without it the launch makes no assumption about x (three
@@ -231,15 +262,7 @@ def conv3d_forward(x, w, b, act, step=None, x_act=False):
     if tuple(w.shape) != (Cout, Cin, 3, 3, 3):
         raise RuntimeError(f"conv3d: weight {tuple(w.shape)} does not match input channels {Cin}")
     _same_shape("conv3d", "bias", b, (Cout,), f"weight {tuple(w.shape)}")
-    y = torch.empty((B, D, H, W, Cout), dtype=torch.float32, device=x.device)
-    L = _L()
-    nb = L.modet_conv3d_ws_bytes(Cin, Cout)
-    ws = _ws(nb, x)
-    n = float(B) * D * H * W
-    with _Guard(x, _conv_tag("fwd", x.shape, Cin, Cout, 1 if act else 0, f16=bool(x_act)), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
-        fn = L.modet_conv3d_fwd_bounded if x_act else L.modet_conv3d_fwd
-        _lib.check(fn(_p(x), _p(w), _p(b), _p(y), _p(ws), nb, B, D, H, W, Cin, Cout, int(act), _stream(), _h(step)), "modet_conv3d_fwd")
-    return y
+    return _conv_fwd(x, w, b, step, bounded=x_act, act=act)[0]
 
 
 def instnorm_stats(x_raw, stats=None, eps=1e-5):
@@ -269,21 +292,10 @@ def conv3d_forward_normin(x_raw, mean, rstd, w, b, want_stats=True, step=None):
     _chk(x_raw, mean, rstd, w, b)
     _conv_args("conv3d_forward_normin", x_raw, w, b)
     step = step if step is not None else current_step()
-    B, D, H, W, Cin = x_raw.shape
-    Cout = w.shape[0]
+    B, Cin = x_raw.shape[0], x_raw.shape[-1]
     _same_shape("conv3d_forward_normin", "mean", mean, (B * Cin,), f"input {tuple(x_raw.shape)}")
     _same_shape("conv3d_forward_normin", "rstd", rstd, (B * Cin,), f"input {tuple(x_raw.shape)}")
-    L = _L()
-    y = torch.empty((B, D, H, W, Cout), dtype=torch.float32, device=x_raw.device)
-    nb = L.modet_conv3d_ws_bytes(Cin, Cout)
-    ws = _ws(nb, x_raw)
-    sb = L.modet_conv3d_normin_stats_bytes(B, D, H, W, Cin, Cout) if want_stats else 0
-    stats = torch.empty(sb // 4, dtype=torch.float32, device=x_raw.device) if sb > 0 else None
-    n = float(B) * D * H * W
-    with _Guard(x_raw, _conv_tag("fwd", x_raw.shape, Cin, Cout, 2), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
-        _lib.check(L.modet_conv3d_fwd_normin(_p(x_raw), _p(mean), _p(rstd), _p(w), _p(b), _p(y), _p(ws), nb, _p(stats), sb,
-                                             B, D, H, W, Cin, Cout, _stream(), _h(step)), "modet_conv3d_fwd_normin")
-    return y, stats
+    return _conv_fwd(x_raw, w, b, step, norm=(mean, rstd), want_stats=want_stats)
 
 
 # ---- gradient magnitudes for the f16 forms of the backward convolutions (round 5).  The z-marching kernels run on two f16 pieces
@@ -309,7 +321,7 @@ def _new_amax(like):
     key = ("amax", B, D, H, W, C)
     use = _FAM_CACHE.get(key)
     if use is None:          # (the consumer's other channel count is not known here; the families split by volume and channel class)
-        use = _FAM_CACHE[key] = _L().modet_conv3d_kernel_family(B, D, H, W, C, C, 1) in (2, 5)
+        use = _FAM_CACHE[key] = _L().modet_conv3d_kernel_family(B, D, H, W, C, C, 1) in _FAM_F16_DGRAD
     return torch.empty(AMAX_FLOATS, dtype=torch.float32, device=like.device) if use else None
 
 
@@ -636,19 +648,7 @@ class _Conv3dStats(Function):
         _conv_args("conv3d_with_stats", x, w, b)
         ctx.step = current_step()
         ctx.x_act = bool(x_act)                 # x is an activation (bounded: see modet_conv3d_bwd_weight_amax)
-        B, D, H, W, Cin = x.shape
-        Cout = w.shape[0]
-        L = _L()
-        y = torch.empty((B, D, H, W, Cout), dtype=torch.float32, device=x.device)
-        nb = L.modet_conv3d_ws_bytes(Cin, Cout)
-        ws = _ws(nb, x)
-        sb = L.modet_conv3d_stats_bytes(B, D, H, W, Cin, Cout)
-        stats = torch.empty(sb // 4, dtype=torch.float32, device=x.device)
-        n = float(B) * D * H * W
-        with _Guard(x, _conv_tag("fwd", x.shape, Cin, Cout, 3, f16=ctx.x_act), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
-            fn = L.modet_conv3d_fwd_stats_bounded if ctx.x_act else L.modet_conv3d_fwd_stats
-            _lib.check(fn(_p(x), _p(w), _p(b), _p(y), _p(ws), nb, _p(stats), sb, B, D, H, W, Cin, Cout, _stream(), _h(ctx.step)),
-                       "modet_conv3d_fwd_stats")
+        y, stats = _conv_fwd(x, w, b, ctx.step, bounded=ctx.x_act, want_stats=True)
         ctx.has_bias = b is not None
         ctx.save_for_backward(x, w, b)
         ctx.mark_non_differentiable(stats)
@@ -676,7 +676,7 @@ def _fuse_stats(x, w, needs_grad=None):
     L = _L()
     if L.modet_conv3d_stats_bytes(B, D, H, W, Cin, Cout) == 0:
         return False
-    if L.modet_conv3d_kernel_family(B, D, H, W, Cin, Cout, 0) in (1, 2, 5):  # the bf16x3 kernels carry the statistics at no cost
+    if L.modet_conv3d_kernel_family(B, D, H, W, Cin, Cout, 0) in _FAM_BF16X3_FWD:
         return True
     if needs_grad is None:     # (inside an autograd.Function.forward grad mode is off: such callers pass their ctx.needs_input_grad)
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)
@@ -758,19 +758,9 @@ class _InstNormConv(Function):
                 ws = _ws(nb, x_raw)
                 _lib.check(L.modet_instnorm_lrelu_fwd(_p(x_raw), _p(y), _p(mean), _p(rstd), _p(ws), nb, B, V, C, eps,
                                                       _stream()), "modet_instnorm_lrelu_fwd")
-        _, D, H, W, Cin = y.shape
-        Cout = w.shape[0]
         stats = None
         if want_stats and _fuse_stats(y, w, needs_grad=any(ctx.needs_input_grad)):
-            z = torch.empty((B, D, H, W, Cout), dtype=torch.float32, device=y.device)
-            nb = L.modet_conv3d_ws_bytes(Cin, Cout)
-            ws = _ws(nb, y)
-            sb = L.modet_conv3d_stats_bytes(B, D, H, W, Cin, Cout)
-            stats = torch.empty(sb // 4, dtype=torch.float32, device=y.device)
-            n = float(B) * D * H * W
-            with _Guard(y, _conv_tag("fwd", y.shape, Cin, Cout, 3, f16=True), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
-                _lib.check(L.modet_conv3d_fwd_stats_bounded(_p(y), _p(w), _p(b), _p(z), _p(ws), nb, _p(stats), sb, B, D, H, W, Cin,
-                                                            Cout, _stream(), _h(ctx.step)), "modet_conv3d_fwd_stats")    # (y: LeakyReLU(InstanceNorm(.)))
+            z, stats = _conv_fwd(y, w, b, ctx.step, bounded=True, want_stats=True)      # (y: LeakyReLU(InstanceNorm(.)))
             ctx.mark_non_differentiable(stats)
         else:
             z = conv3d_forward(y, w, b, False, ctx.step, x_act=True)

@@ -68,6 +68,28 @@ def test_header_is_plain_c_and_the_ctypes_structs_match_it(tmp_path):
     assert got[7] == 16
 
 
+def test_conv_routing_matches_the_recorded_table():
+    """Which kernel family runs each fp32 convolution, and the size / capability queries that must follow the same route,
+    against tests/golden/conv_routing.npz over its whole grid (44 688 family entries; host-only queries).  The table was
+    recorded by tests/golden/make_conv_routing.py BEFORE the dispatch code was last restructured: an entry that moved is
+    a routing change, which only a deliberate change of the policy may make (and then re-records the table)."""
+    import importlib.util
+    from smilecode_amd import _lib
+    spec = importlib.util.spec_from_file_location("make_conv_routing", os.path.join(ROOT, "tests", "golden", "make_conv_routing.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want = np.load(os.path.join(ROOT, "tests", "golden", "conv_routing.npz"))
+    assert want["family"].size == 44688 and want["family"].dtype == np.int8
+    for fam in range(6):       # a table that lost a family pins nothing about it
+        assert (want["family"] == fam).any(), f"family {fam} does not occur in the recorded table"
+    got = gen.table(_lib.load())
+    assert sorted(got) == sorted(want.files)
+    for name in want.files:
+        bad = np.argwhere(got[name] != want[name])
+        where = [(gen.VOLUMES[i[0]], gen.CHANNELS[i[1]], gen.CHANNELS[i[2]]) + tuple(int(v) for v in i[3:]) for i in bad[:5]]
+        assert len(bad) == 0, f"{name}: {len(bad)} entries moved, first (volume, Cin, Cout[, pass, variant]): {where}"
+
+
 def test_product_path_has_no_cpu_fallback():
     from smilecode_amd import ops
     x = torch.zeros(1, 4, 4, 4, 8)
