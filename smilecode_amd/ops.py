@@ -28,6 +28,11 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _call(fn, *args):
+    """every library call: a failure names the entry point that was entered"""
+    _lib.check(fn(*args), fn.__name__)
+
+
 def _chk(*ts):
     for t in ts:
         if t is None:
@@ -240,13 +245,13 @@ def _conv_fwd(x, w, b, step, bounded=False, act=False, norm=None, want_stats=Fal
     out, dims = (_p(w), _p(b), _p(y), _p(ws), nb), (B, D, H, W, Cin, Cout)
     with _Guard(x, _conv_tag("fwd", x.shape, Cin, Cout, variant, f16=bool(bounded or norm)), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
         if norm:
-            _lib.check(L.modet_conv3d_fwd_normin(_p(x), *map(_p, norm), *out, _p(stats), sb, *dims, _stream(), _h(step)), "modet_conv3d_fwd_normin")
+            _call(L.modet_conv3d_fwd_normin, _p(x), *map(_p, norm), *out, _p(stats), sb, *dims, _stream(), _h(step))
         elif want_stats:
             fn = L.modet_conv3d_fwd_stats_bounded if bounded else L.modet_conv3d_fwd_stats
-            _lib.check(fn(_p(x), *out, _p(stats), sb, *dims, _stream(), _h(step)), "modet_conv3d_fwd_stats")
+            _call(fn, _p(x), *out, _p(stats), sb, *dims, _stream(), _h(step))
         else:
             fn = L.modet_conv3d_fwd_bounded if bounded else L.modet_conv3d_fwd
-            _lib.check(fn(_p(x), *out, *dims, int(act), _stream(), _h(step)), "modet_conv3d_fwd")
+            _call(fn, _p(x), *out, *dims, int(act), _stream(), _h(step))
     return y, stats
 
 
@@ -269,21 +274,62 @@ def instnorm_stats(x_raw, stats=None, eps=1e-5):
     """per-(sample, channel) mean / rstd of a raw conv output, without the apply pass: from the conv epilogue's partial
     statistics when given, else by one statistics pass over x_raw"""
     _chk(x_raw)
-    B, C = x_raw.shape[0], x_raw.shape[-1]
-    V = x_raw.numel() // (B * C)
-    mean = torch.empty(B * C, dtype=torch.float32, device=x_raw.device)
-    rstd = torch.empty_like(mean)
-    L = _L()
     with _Guard(x_raw, "instnorm_stats", 2.0 * x_raw.numel(), 0.0 if stats is not None else 4.0 * x_raw.numel()):
+        return _in_stats(x_raw, stats, eps)
+
+
+# ---- the fp32 InstanceNorm launches (arguments already checked), one function per library call as _conv_fwd.
+# ``stats`` = the producing conv's partial statistics, None = one pass more over x.
+def _in_dims(x):
+    """(B, V, C) of a channels-last tensor and fresh (mean, rstd) buffers of its B * C instances"""
+    B, C = x.shape[0], x.shape[-1]
+    mean = torch.empty(B * C, dtype=torch.float32, device=x.device)
+    return B, x.numel() // (B * C), C, mean, torch.empty_like(mean)
+
+
+def _in_stats(x, stats, eps, pass_x=False):
+    """THE statistics-only launch -> (mean, rstd), inside the caller's bracket (the pool node times it with its apply pass).
+    With stats the kernel never reads x (csrc/norm_act.hip); pass_x hands its address over all the same, as the pool node has."""
+    B, V, C, mean, rstd = _in_dims(x)
+    L = _L()
+    if stats is not None:
+        _call(L.modet_instnorm_stats, _p(x) if pass_x else None, _p(mean), _p(rstd), _p(stats), stats.numel() * 4, None, 0, B, V, C,
+              eps, _stream())
+    else:
+        nb = L.modet_instnorm_ws_bytes(B, V, C)
+        ws = _ws(nb, x)
+        _call(L.modet_instnorm_stats, _p(x), _p(mean), _p(rstd), None, 0, _p(ws), nb, B, V, C, eps, _stream())
+    return mean, rstd
+
+
+def _in_fwd(x, stats, eps):
+    """THE InstanceNorm + LeakyReLU forward launch -> (y, mean, rstd)"""
+    B, V, C, mean, rstd = _in_dims(x)
+    y = torch.empty_like(x)
+    L = _L()
+    with _Guard(x, "instnorm_lrelu_fwd", 8.0 * x.numel(), 8.0 * x.numel()):
         if stats is not None:
-            _lib.check(L.modet_instnorm_stats(None, _p(mean), _p(rstd), _p(stats), stats.numel() * 4, None, 0, B, V, C, eps,
-                                              _stream()), "modet_instnorm_stats")
+            _call(L.modet_instnorm_lrelu_fwd_stats, _p(x), _p(y), _p(mean), _p(rstd), _p(stats), stats.numel() * 4, B, V, C, eps,
+                  _stream())
         else:
             nb = L.modet_instnorm_ws_bytes(B, V, C)
-            ws = _ws(nb, x_raw)
-            _lib.check(L.modet_instnorm_stats(_p(x_raw), _p(mean), _p(rstd), None, 0, _p(ws), nb, B, V, C, eps, _stream()),
-                       "modet_instnorm_stats")
-    return mean, rstd
+            ws = _ws(nb, x)
+            _call(L.modet_instnorm_lrelu_fwd, _p(x), _p(y), _p(mean), _p(rstd), _p(ws), nb, B, V, C, eps, _stream())
+    return y, mean, rstd
+
+
+def _in_bwd(dy, x, mean, rstd):
+    """THE InstanceNorm + LeakyReLU backward launch -> d_x, tagged with the fresh buffer the kernel left max |d_x| in (_new_amax)"""
+    B, C = x.shape[0], x.shape[-1]
+    V = x.numel() // (B * C)
+    dx = torch.empty_like(x)
+    amax = _new_amax(x)
+    L = _L()
+    nb = L.modet_instnorm_ws_bytes(B, V, C)
+    ws = _ws(nb, x)
+    with _Guard(x, "instnorm_lrelu_bwd", 14.0 * x.numel(), 12.0 * x.numel()):
+        _call(L.modet_instnorm_lrelu_bwd_amax, _p(dy), _p(x), _p(mean), _p(rstd), _p(dx), _p(ws), nb, B, V, C, _p(amax), _stream())
+    return _tag_amax(dx, amax)
 
 
 def conv3d_forward_normin(x_raw, mean, rstd, w, b, want_stats=True, step=None):
@@ -357,8 +403,7 @@ def conv3d_backward_data(dy, w, Cin, step=None, amax=None):
     ws = _ws(nb, dy)
     n = float(B) * D * H * W
     with _Guard(dy, _conv_tag("dgrad", dy.shape, Cin, Cout, f16=amax is not None), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
-        _lib.check(L.modet_conv3d_bwd_data_amax(_p(dy), _p(w), _p(dx), _p(ws), nb, B, D, H, W, Cin, Cout, _p(amax), _stream(),
-                                                _h(step)), "modet_conv3d_bwd_data")
+        _call(L.modet_conv3d_bwd_data_amax, _p(dy), _p(w), _p(dx), _p(ws), nb, B, D, H, W, Cin, Cout, _p(amax), _stream(), _h(step))
     return dx
 
 
@@ -383,7 +428,7 @@ class StepContext:
     def __init__(self):
         import ctypes
         h = ctypes.c_void_p()
-        _lib.check(_L().modet_step_ctx_create(ctypes.byref(h)), "modet_step_ctx_create")
+        _call(_L().modet_step_ctx_create, ctypes.byref(h))
         self.handle = h
         self.arena = None            # packed weights of every recorded conv launch (fp32 jobs, then the 16-bit ones)
         self.recorded = False
@@ -418,8 +463,7 @@ class StepContext:
             if self.recording:
                 L.modet_conv3d_prepack_record(sc.handle, 1)
             else:
-                _lib.check(L.modet_conv3d_prepack_begin(sc.handle, _p(sc.arena), sc.arena.numel() * 4, _stream()),
-                           "modet_conv3d_prepack_begin")
+                _call(L.modet_conv3d_prepack_begin, sc.handle, _p(sc.arena), sc.arena.numel() * 4, _stream())
             return super().__enter__()
 
         def __exit__(self, *exc):
@@ -457,7 +501,7 @@ class StepContext:
             jobs, sc._leaf = sc._leaf, []
             if exc[0] is None and jobs:                  # the attention / projection parameter gradients of every level: one launch
                 arr = (_lib.LeafJob * len(jobs))(*jobs)            # host table: copied into the launch's arguments
-                _lib.check(_L().modet_leaf_reduce_many(ctypes.addressof(arr), len(jobs), _stream()), "modet_leaf_reduce_many")
+                _call(_L().modet_leaf_reduce_many, ctypes.addressof(arr), len(jobs), _stream())
             sc._keep = []
             if exc[0] is None:
                 _lib.check(rc, "modet_conv3d_wgrad_defer_flush")
@@ -586,7 +630,7 @@ def conv3d_backward_weight(x, dy, want_bias, y_act=None, w=None, b=None, step=No
         else:
             fn, head, tail = L.modet_conv3d_bwd_weight, (x, dy), (_stream(),)
         with _Guard(x, _conv_tag("wgrad", x.shape, Cin, Cout, f16=f16), 54.0 * Cin * Cout * n, 4.0 * n * (Cin + Cout)):
-            _lib.check(fn(*map(_p, head), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin, Cout, *tail), fn.__name__)
+            _call(fn, *map(_p, head), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin, Cout, *tail)
 
     scope = step if step is not None else current_step()
     dst = scope.destinations(w, b, want_bias) if scope is not None else None
@@ -631,7 +675,7 @@ class _Conv3d(Function):
         if ctx.act:
             g = torch.empty_like(dy)
             with _Guard(dy, "lrelu_bwd", dy.numel(), 12.0 * dy.numel()):
-                _lib.check(_L().modet_lrelu_bwd(_p(dy), _p(y), _p(g), dy.numel(), _stream()), "modet_lrelu_bwd")
+                _call(_L().modet_lrelu_bwd, _p(dy), _p(y), _p(g), dy.numel(), _stream())
             dy = g
         amax = None if ctx.act else _amax_of(dy)                 # (x is whatever the caller convolved: no f16 weight gradient)
         dw, db = conv3d_backward_weight(x, dy, ctx.has_bias, w=w, b=b, step=ctx.step)
@@ -731,11 +775,9 @@ class _InstNormConv(Function):
         _conv_args("lazy_instnorm_conv3d", x_raw, w, b)
         ctx.step = current_step()
         B, C = x_raw.shape[0], x_raw.shape[-1]
-        V = x_raw.numel() // (B * C)
-        L = _L()
         ctx.lazy = False
         if (LAZY_IN_TRAIN and x_raw.dim() == 5 and C % 4 == 0 and
-                L.modet_conv3d_bwd_weight_normin_ok(B, x_raw.shape[1], x_raw.shape[2], x_raw.shape[3], C, w.shape[0])):
+                _L().modet_conv3d_bwd_weight_normin_ok(B, x_raw.shape[1], x_raw.shape[2], x_raw.shape[3], C, w.shape[0])):
             mean, rstd = instnorm_stats(x_raw, stats_in, eps)
             z, stats = conv3d_forward_normin(x_raw, mean, rstd, w, b, want_stats, ctx.step)
             if stats is not None:
@@ -745,19 +787,7 @@ class _InstNormConv(Function):
             ctx.lazy = True
             ctx.save_for_backward(x_raw, mean, rstd, None, w, b)
             return z, stats
-        y = torch.empty_like(x_raw)
-        mean = torch.empty(B * C, dtype=torch.float32, device=x_raw.device)
-        rstd = torch.empty_like(mean)
-        with _Guard(x_raw, "instnorm_lrelu_fwd", 8.0 * x_raw.numel(), 8.0 * x_raw.numel()):
-            if stats_in is not None:
-                _lib.check(L.modet_instnorm_lrelu_fwd_stats(_p(x_raw), _p(y), _p(mean), _p(rstd), _p(stats_in),
-                                                            stats_in.numel() * 4, B, V, C, eps, _stream()),
-                           "modet_instnorm_lrelu_fwd_stats")
-            else:
-                nb = L.modet_instnorm_ws_bytes(B, V, C)
-                ws = _ws(nb, x_raw)
-                _lib.check(L.modet_instnorm_lrelu_fwd(_p(x_raw), _p(y), _p(mean), _p(rstd), _p(ws), nb, B, V, C, eps,
-                                                      _stream()), "modet_instnorm_lrelu_fwd")
+        y, mean, rstd = _in_fwd(x_raw, stats_in, eps)
         stats = None
         if want_stats and _fuse_stats(y, w, needs_grad=any(ctx.needs_input_grad)):
             z, stats = _conv_fwd(y, w, b, ctx.step, bounded=True, want_stats=True)      # (y: LeakyReLU(InstanceNorm(.)))
@@ -786,33 +816,26 @@ class _InstNormConv(Function):
         else:
             dw, db = conv3d_backward_weight(y, dz, ctx.has_bias, w=w, b=b, step=ctx.step, amax=amax)   # (first: see _Conv3d.backward)
         if ctx.needs_input_grad[0]:
-            d_raw = torch.empty_like(x_raw)
-            amax_raw = _new_amax(x_raw)
             rb = L.modet_conv3d_bwd_data_instats_bytes(B, D, H, W, C, Cout) if FUSE_IN_DGRAD else 0
             if rb > 0:
+                d_raw = torch.empty_like(x_raw)
+                amax_raw = _new_amax(x_raw)
                 d_y = torch.empty_like(x_raw)
                 rows = torch.empty(rb // 4, dtype=torch.float32, device=x_raw.device)
                 nb = L.modet_conv3d_ws_bytes(C, Cout)
                 ws = _ws(nb, dz)
                 n = float(B) * V
                 with _Guard(dz, _conv_tag("dgrad", dz.shape, C, Cout, f16=amax is not None), 54.0 * C * Cout * n, 4.0 * n * (2 * C + Cout)):
-                    _lib.check(L.modet_conv3d_bwd_data_instats_amax(_p(dz), _p(w), _p(d_y), _p(x_raw), _p(mean), _p(rstd), _p(rows),
-                                                                    rb, _p(ws), nb, B, D, H, W, C, Cout, _p(amax), _stream(),
-                                                                    _h(ctx.step)), "modet_conv3d_bwd_data_instats")
+                    _call(L.modet_conv3d_bwd_data_instats_amax, _p(dz), _p(w), _p(d_y), _p(x_raw), _p(mean), _p(rstd), _p(rows), rb,
+                          _p(ws), nb, B, D, H, W, C, Cout, _p(amax), _stream(), _h(ctx.step))
                 nb2 = 2 * B * C * 4
                 ws2 = _ws(nb2, x_raw)
                 with _Guard(x_raw, "instnorm_lrelu_bwd", 7.0 * x_raw.numel(), 12.0 * x_raw.numel()):
-                    _lib.check(L.modet_instnorm_lrelu_bwd_rows_amax(_p(d_y), _p(x_raw), _p(mean), _p(rstd), _p(d_raw), _p(rows), rb,
-                                                                    _p(ws2), nb2, B, V, C, _p(amax_raw), _stream()),
-                               "modet_instnorm_lrelu_bwd_rows")
+                    _call(L.modet_instnorm_lrelu_bwd_rows_amax, _p(d_y), _p(x_raw), _p(mean), _p(rstd), _p(d_raw), _p(rows), rb,
+                          _p(ws2), nb2, B, V, C, _p(amax_raw), _stream())
+                _tag_amax(d_raw, amax_raw)
             else:
-                d_y = conv3d_backward_data(dz, w, C, ctx.step, amax)
-                nb = L.modet_instnorm_ws_bytes(B, V, C)
-                ws = _ws(nb, x_raw)
-                with _Guard(x_raw, "instnorm_lrelu_bwd", 14.0 * x_raw.numel(), 12.0 * x_raw.numel()):
-                    _lib.check(L.modet_instnorm_lrelu_bwd_amax(_p(d_y), _p(x_raw), _p(mean), _p(rstd), _p(d_raw), _p(ws), nb, B, V, C,
-                                                               _p(amax_raw), _stream()), "modet_instnorm_lrelu_bwd")
-            _tag_amax(d_raw, amax_raw)
+                d_raw = _in_bwd(conv3d_backward_data(dz, w, C, ctx.step, amax), x_raw, mean, rstd)
         return d_raw, None, dw, db, None, None
 
 
@@ -835,40 +858,14 @@ class _InstNormLReLU(Function):
     @staticmethod
     def forward(ctx, x, eps, stats=None):
         _chk(x)
-        B, C = x.shape[0], x.shape[-1]
-        V = x.numel() // (B * C)
-        y = torch.empty_like(x)
-        mean = torch.empty(B * C, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        L = _L()
-        if stats is not None:
-            with _Guard(x, "instnorm_lrelu_fwd", 8.0 * x.numel(), 8.0 * x.numel()):
-                _lib.check(L.modet_instnorm_lrelu_fwd_stats(_p(x), _p(y), _p(mean), _p(rstd), _p(stats), stats.numel() * 4,
-                                                            B, V, C, eps, _stream()), "modet_instnorm_lrelu_fwd_stats")
-        else:
-            nb = L.modet_instnorm_ws_bytes(B, V, C)
-            ws = _ws(nb, x)
-            with _Guard(x, "instnorm_lrelu_fwd", 8.0 * x.numel(), 8.0 * x.numel()):
-                _lib.check(L.modet_instnorm_lrelu_fwd(_p(x), _p(y), _p(mean), _p(rstd), _p(ws), nb, B, V, C, eps,
-                                                      _stream()), "modet_instnorm_lrelu_fwd")
+        y, mean, rstd = _in_fwd(x, stats, eps)
         ctx.save_for_backward(x, mean, rstd)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, mean, rstd = ctx.saved_tensors
-        dy = dy.contiguous()
-        B, C = x.shape[0], x.shape[-1]
-        V = x.numel() // (B * C)
-        dx = torch.empty_like(x)
-        amax = _new_amax(x)
-        L = _L()
-        nb = L.modet_instnorm_ws_bytes(B, V, C)
-        ws = _ws(nb, x)
-        with _Guard(x, "instnorm_lrelu_bwd", 14.0 * x.numel(), 12.0 * x.numel()):
-            _lib.check(L.modet_instnorm_lrelu_bwd_amax(_p(dy), _p(x), _p(mean), _p(rstd), _p(dx), _p(ws), nb, B, V, C, _p(amax),
-                                                       _stream()), "modet_instnorm_lrelu_bwd")
-        return _tag_amax(dx, amax), None, None
+        return _in_bwd(dy.contiguous(), x, mean, rstd), None, None
 
 
 def instnorm_lrelu(x, eps=1e-5):
@@ -876,26 +873,49 @@ def instnorm_lrelu(x, eps=1e-5):
     return _InstNormLReLU.apply(x, eps, None)
 
 
+def _pool_fwd(x):
+    """THE AvgPool3d(2) forward launch (x: a checked fp32 (B,D,H,W,C) tensor)"""
+    B, D, H, W, C = x.shape
+    y = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
+    with _Guard(x, "avgpool2_fwd", x.numel(), 4.5 * x.numel()):
+        _call(_L().modet_avgpool2_fwd, _p(x), _p(y), B, D, H, W, C, _stream())
+    return y
+
+
+def _pool_bwd(gy, shape, parts, nbytes):
+    """THE AvgPool3d(2) backward: d_x = unpool(gy) / 8 + addend, one launch per (lo, hi, addend or None) batch range of
+    ``parts`` inside one bracket; nbytes: the bracket's bytes per element of d_x"""
+    D, H, W, C = shape[1:]
+    dx = torch.empty(shape, dtype=torch.float32, device=gy.device)
+    with _Guard(gy, "avgpool2_bwd", dx.numel(), nbytes * dx.numel()):
+        for lo, hi, add in parts:
+            add = None if add is None else add.contiguous()
+            _call(_L().modet_avgpool2_bwd, _p(gy[lo:hi]), _p(add), _p(dx[lo:hi]), hi - lo, D, H, W, C, _stream())
+    return dx
+
+
+def _halves(ga, gb, Bh, shape):
+    """[ga ; gb] as one fp32 tensor of ``shape``, zeros for an absent half"""
+    g = torch.empty(shape, dtype=torch.float32, device=(ga if ga is not None else gb).device)
+    for part, src in ((g[:Bh], ga), (g[Bh:], gb)):
+        if src is None:
+            part.zero_()
+        else:
+            part.copy_(src)
+    return g
+
+
 class _AvgPool2(Function):
     @staticmethod
     def forward(ctx, x):
         _chk(x)
         _rank5("avgpool2", "x", x)
-        B, D, H, W, C = x.shape
-        y = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
-        with _Guard(x, "avgpool2_fwd", x.numel(), 4.5 * x.numel()):
-            _lib.check(_L().modet_avgpool2_fwd(_p(x), _p(y), B, D, H, W, C, _stream()), "modet_avgpool2_fwd")
-        ctx.shape = (B, D, H, W, C)
-        return y
+        ctx.shape = tuple(x.shape)
+        return _pool_fwd(x)
 
     @staticmethod
     def backward(ctx, dy):
-        dy = dy.contiguous()
-        B, D, H, W, C = ctx.shape
-        dx = torch.empty(ctx.shape, dtype=torch.float32, device=dy.device)
-        with _Guard(dy, "avgpool2_bwd", dx.numel(), 4.5 * dx.numel()):
-            _lib.check(_L().modet_avgpool2_bwd(_p(dy), None, _p(dx), B, D, H, W, C, _stream()), "modet_avgpool2_bwd")
-        return dx
+        return _pool_bwd(dy.contiguous(), ctx.shape, ((0, ctx.shape[0], None),), 4.5)
 
 
 def avgpool2(x):
@@ -912,24 +932,15 @@ class _PoolTee(Function):
     def forward(ctx, x):
         _chk(x)
         _rank5("pool_tee", "x", x)
-        B, D, H, W, C = x.shape
-        y = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
-        with _Guard(x, "avgpool2_fwd", x.numel(), 4.5 * x.numel()):
-            _lib.check(_L().modet_avgpool2_fwd(_p(x), _p(y), B, D, H, W, C, _stream()), "modet_avgpool2_fwd")
-        ctx.shape = (B, D, H, W, C)
-        return y, x.view_as(x)
+        ctx.shape = tuple(x.shape)
+        return _pool_fwd(x), x.view_as(x)
 
     @staticmethod
     def backward(ctx, gy, gx):
-        B, D, H, W, C = ctx.shape
         if gy is None:
             return gx
-        gy = gy.contiguous()
-        add = None if gx is None else gx.contiguous()
-        dx = torch.empty(ctx.shape, dtype=torch.float32, device=gy.device)
-        with _Guard(gy, "avgpool2_bwd", dx.numel(), 4.5 * dx.numel() + (4.0 * dx.numel() if add is not None else 0.0)):
-            _lib.check(_L().modet_avgpool2_bwd(_p(gy), _p(add), _p(dx), B, D, H, W, C, _stream()), "modet_avgpool2_bwd")
-        return dx
+        gx = None if gx is None else gx.contiguous()
+        return _pool_bwd(gy.contiguous(), ctx.shape, ((0, ctx.shape[0], gx),), 4.5 if gx is None else 8.5)
 
 
 def pool_tee(x):
@@ -949,33 +960,16 @@ class _PoolTeeSplit(Function):
         B, D, H, W, C = x.shape
         if not 0 < Bh < B:
             raise RuntimeError(f"pool_tee_split: split {Bh} is not inside the batch of {tuple(x.shape)}")
-        y = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
-        with _Guard(x, "avgpool2_fwd", x.numel(), 4.5 * x.numel()):
-            _lib.check(_L().modet_avgpool2_fwd(_p(x), _p(y), B, D, H, W, C, _stream()), "modet_avgpool2_fwd")
         ctx.shape = (B, D, H, W, C)
         ctx.Bh = Bh
-        return y, x[:Bh], x[Bh:]
+        return _pool_fwd(x), x[:Bh], x[Bh:]
 
     @staticmethod
     def backward(ctx, gy, ga, gb):
-        B, D, H, W, C = ctx.shape
-        Bh = ctx.Bh
-        dx = torch.empty(ctx.shape, dtype=torch.float32, device=(gy if gy is not None else ga if ga is not None else gb).device)
+        B, Bh = ctx.shape[0], ctx.Bh
         if gy is None:
-            for sl, g in ((slice(0, Bh), ga), (slice(Bh, B), gb)):
-                if g is None:
-                    dx[sl].zero_()
-                else:
-                    dx[sl].copy_(g)
-            return dx, None
-        gy = gy.contiguous()
-        L = _L()
-        with _Guard(gy, "avgpool2_bwd", dx.numel(), 8.5 * dx.numel()):
-            for lo, hi, g in ((0, Bh, ga), (Bh, B, gb)):
-                add = None if g is None else g.contiguous()
-                _lib.check(L.modet_avgpool2_bwd(_p(gy[lo:hi]), _p(add), _p(dx[lo:hi]), hi - lo, D, H, W, C, _stream()),
-                           "modet_avgpool2_bwd")
-        return dx, None
+            return _halves(ga, gb, Bh, ctx.shape), None
+        return _pool_bwd(gy.contiguous(), ctx.shape, ((0, Bh, ga), (Bh, B, gb)), 8.5), None
 
 
 def pool_tee_split(x, Bh):
@@ -996,23 +990,11 @@ class _InstNormLReLUPoolSplit(Function):
         B, D, H, W, C = x.shape
         if not 0 < Bh < B:
             raise RuntimeError(f"instnorm_lrelu_pool_tee_split: split {Bh} is not inside the batch of {tuple(x.shape)}")
-        V = D * H * W
-        L = _L()
-        mean = torch.empty(B * C, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
         y = torch.empty_like(x)
         pooled = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
         with _Guard(x, "instnorm_lrelu_fwd", 9.0 * x.numel(), 8.5 * x.numel()):
-            if stats is not None:
-                _lib.check(L.modet_instnorm_stats(_p(x), _p(mean), _p(rstd), _p(stats), stats.numel() * 4, None, 0, B, V, C,
-                                                  eps, _stream()), "modet_instnorm_stats")
-            else:
-                nb = L.modet_instnorm_ws_bytes(B, V, C)
-                ws = _ws(nb, x)
-                _lib.check(L.modet_instnorm_stats(_p(x), _p(mean), _p(rstd), None, 0, _p(ws), nb, B, V, C, eps, _stream()),
-                           "modet_instnorm_stats")
-            _lib.check(L.modet_instnorm_lrelu_apply_pool(_p(x), _p(mean), _p(rstd), _p(y), _p(pooled), B, D, H, W, C,
-                                                         _stream()), "modet_instnorm_lrelu_apply_pool")
+            mean, rstd = _in_stats(x, stats, eps, pass_x=True)
+            _call(_L().modet_instnorm_lrelu_apply_pool, _p(x), _p(mean), _p(rstd), _p(y), _p(pooled), B, D, H, W, C, _stream())
         ctx.save_for_backward(x, mean, rstd)
         ctx.Bh = Bh
         ctx.set_materialize_grads(False)        # an unused output arrives as None (no zeros fill launch); handled below
@@ -1025,31 +1007,20 @@ class _InstNormLReLUPoolSplit(Function):
         x, mean, rstd = ctx.saved_tensors
         B, D, H, W, C = x.shape
         Bh = ctx.Bh
-        V = D * H * W
-        L = _L()
+        if gy is None:
+            return _in_bwd(_halves(ga, gb, Bh, x.shape), x, mean, rstd), None, None, None
+        # d_y = unpool(gy) / 8 + [ga ; gb] is formed inside the two InstanceNorm backward passes, never written
+        gy = gy.contiguous()
+        ga = None if ga is None else ga.contiguous()
+        gb = None if gb is None else gb.contiguous()
         dx = torch.empty_like(x)
         amax = _new_amax(x)
-        nb = L.modet_instnorm_ws_bytes(B, V, C)
+        L = _L()
+        nb = L.modet_instnorm_ws_bytes(B, D * H * W, C)
         ws = _ws(nb, x)
-        if gy is not None:
-            # d_y = unpool(gy) / 8 + [ga ; gb] is formed inside the two InstanceNorm backward passes, never written
-            gy = gy.contiguous()
-            ga = None if ga is None else ga.contiguous()
-            gb = None if gb is None else gb.contiguous()
-            with _Guard(x, "instnorm_lrelu_bwd", 15.0 * x.numel(), 12.5 * x.numel()):
-                _lib.check(L.modet_instnorm_lrelu_bwd_pool_amax(_p(gy), _p(ga), _p(gb), Bh, _p(x), _p(mean), _p(rstd), _p(dx), _p(ws),
-                                                                nb, B, D, H, W, C, _p(amax), _stream()),
-                           "modet_instnorm_lrelu_bwd_pool")
-            return _tag_amax(dx, amax), None, None, None
-        dy = torch.empty_like(x)
-        for sl, g in ((slice(0, Bh), ga), (slice(Bh, B), gb)):
-            if g is None:
-                dy[sl].zero_()
-            else:
-                dy[sl].copy_(g)
-        with _Guard(x, "instnorm_lrelu_bwd", 14.0 * x.numel(), 12.0 * x.numel()):
-            _lib.check(L.modet_instnorm_lrelu_bwd_amax(_p(dy), _p(x), _p(mean), _p(rstd), _p(dx), _p(ws), nb, B, V, C, _p(amax),
-                                                       _stream()), "modet_instnorm_lrelu_bwd")
+        with _Guard(x, "instnorm_lrelu_bwd", 15.0 * x.numel(), 12.5 * x.numel()):
+            _call(L.modet_instnorm_lrelu_bwd_pool_amax, _p(gy), _p(ga), _p(gb), Bh, _p(x), _p(mean), _p(rstd), _p(dx), _p(ws), nb,
+                  B, D, H, W, C, _p(amax), _stream())
         return _tag_amax(dx, amax), None, None, None
 
 
@@ -1067,6 +1038,78 @@ def _proj_args(op, Cin, Wt, b, gamma, beta):
         _same_shape(op, name, t, (Wt.shape[0],), f"weight {tuple(Wt.shape)}")
 
 
+def _param_dsts(step, *params):
+    """where a matching node's backward writes its parameter gradients -> (destinations, later, what goes back to autograd).
+    Claimed from the step's deferred() scope (StepContext.claim): written in place, autograd gets None for each, and ``later``
+    says that the kernel leaves partial rows which the scope's one leaf-reduction launch sums (DEFER_LEAF_REDUCTIONS).
+    Otherwise fresh tensors, reduced by the launch itself and returned to autograd."""
+    dst = step.claim(*params) if step is not None else None
+    if dst is not None:
+        return dst, DEFER_LEAF_REDUCTIONS, [None] * len(params)
+    dst = [torch.empty_like(p) for p in params]
+    return dst, False, dst
+
+
+def _proj_pair_bwd(x1, dy1, x2, dy2, Wt, b, gamma, eps, step, dsts, later, typed=False):
+    """THE paired projection backward launch -> (d_x1, d_x2), fp32; dsts = (d_W, d_bias, d_gamma, d_beta) of _param_dsts.
+    typed: the bf16-storage node's entry point (modet_proj_ln_bwd_pair_t: each input fp32 or bf16), whose byte figure counts
+    one bf16 and one fp32 input; the fp32 node keeps the plain one."""
+    Cin, dim = x1.shape[-1], Wt.shape[0]
+    N = x1.numel() // Cin
+    L = _L()
+    dx1 = torch.empty(x1.shape, dtype=torch.float32, device=x1.device)
+    dx2 = torch.empty(x2.shape, dtype=torch.float32, device=x2.device)
+    nb = L.modet_proj_ln_bwd_pair_ws_bytes(N, Cin, dim)
+    if nb == 0:
+        raise RuntimeError(f"{'level attention (bf16)' if typed else 'proj_ln_pair'}: no paired projection backward for Cin {Cin}, dim {dim}")
+    ws = _ws(nb, x1)
+    out4 = map(_p, (None, None, None, None) if later else dsts)
+    with _Guard(x1, f"proj_ln_bwd[{Cin}->{dim}]", 2.0 * N * (6.0 * Cin * dim + 20.0 * dim), N * ((14.0 if typed else 16.0) * Cin + 8.0 * dim)):
+        if typed:
+            _call(L.modet_proj_ln_bwd_pair_t, _p(x1), _isbf(x1), _p(dy1), _p(dx1), _p(x2), _isbf(x2), _p(dy2), _p(dx2), _p(Wt), _p(b),
+                  _p(gamma), *out4, _p(ws), nb, N, Cin, dim, eps, _stream())
+        else:
+            _call(L.modet_proj_ln_bwd_pair, _p(x1), _p(dy1), _p(dx1), _p(x2), _p(dy2), _p(dx2), _p(Wt), _p(b), _p(gamma), *out4,
+                  _p(ws), nb, N, Cin, dim, eps, _stream())
+    if later:
+        _defer_proj(step, ws, N, Cin, dim, *dsts)
+    return dx1, dx2
+
+
+def _na_fwd(q, k, rpb, heads, scale, need_grad):
+    """THE attention forward launch -> (out, lse or None): modet_na_fwd for fp32 q / k, modet_na_fwd_t for bf16 ones"""
+    B, D, H, W, C = q.shape
+    typed = q.dtype == torch.bfloat16
+    L = _L()
+    out = torch.empty((B, D, H, W, heads * 3), dtype=torch.float32, device=q.device)
+    lse = torch.empty((B, D, H, W, heads), dtype=torch.float32, device=q.device) if need_grad else None
+    nvh = float(B) * D * H * W * heads      # 12 elements of q,k + 12 B of out, ~620 flop per voxel-head (SURVEY.md §8d)
+    head = (_p(q), _p(k), 1) if typed else (_p(q), _p(k))
+    with _Guard(q, f"na_fwd[h{heads}]", 620.0 * nvh, (12.0 + 12.0 * q.element_size()) * nvh):
+        _call(L.modet_na_fwd_t if typed else L.modet_na_fwd, *head, _p(rpb), _p(out), _p(lse), B, D, H, W, heads, C // heads,
+              float(scale), _stream())
+    return out, lse
+
+
+def _na_bwd(q, k, rpb, out, lse, dout, heads, scale, step, drpb, later):
+    """THE attention backward launch -> (d_q, d_k), fp32; entry point by q's dtype as _na_fwd; drpb: _param_dsts' destination"""
+    B, D, H, W, C = q.shape
+    typed = q.dtype == torch.bfloat16
+    L = _L()
+    dq = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    dk = torch.empty_like(dq)
+    nb = L.modet_na_bwd_ws_bytes(B, D, H, W, heads)
+    ws = _ws(nb, q)
+    nvh = float(B) * D * H * W * heads      # reads q,k (12 elements), d_out,out,lse (7 floats), writes d_q,d_k (12)
+    head = (_p(q), _p(k), 1) if typed else (_p(q), _p(k))
+    with _Guard(q, f"na_bwd[h{heads}]", 1900.0 * nvh, (76.0 + 12.0 * q.element_size()) * nvh):
+        _call(L.modet_na_bwd_t if typed else L.modet_na_bwd, *head, _p(rpb), _p(out), _p(lse), _p(dout), _p(dq), _p(dk),
+              _p(None if later else drpb), _p(ws), nb, B, D, H, W, heads, C // heads, scale, _stream())
+    if later:
+        _defer_rpb(step, ws, B, D, H, W, heads, C // heads, drpb)
+    return dq, dk
+
+
 class _ProjLN(Function):
     @staticmethod
     def forward(ctx, x, Wt, b, gamma, beta, eps):
@@ -1077,8 +1120,7 @@ class _ProjLN(Function):
         N = x.numel() // Cin
         y = torch.empty(x.shape[:-1] + (dim,), dtype=torch.float32, device=x.device)
         with _Guard(x, f"proj_ln_fwd[{Cin}->{dim}]", N * (2.0 * Cin * dim + 8.0 * dim), 4.0 * N * (Cin + dim)):
-            _lib.check(_L().modet_proj_ln_fwd(_p(x), _p(Wt), _p(b), _p(gamma), _p(beta), _p(y), N, Cin, dim, eps,
-                                              _stream()), "modet_proj_ln_fwd")
+            _call(_L().modet_proj_ln_fwd, _p(x), _p(Wt), _p(b), _p(gamma), _p(beta), _p(y), N, Cin, dim, eps, _stream())
         ctx.save_for_backward(x, Wt, b, gamma, beta)
         ctx.eps = eps
         ctx.step = current_step()
@@ -1092,18 +1134,14 @@ class _ProjLN(Function):
         dim = Wt.shape[0]
         N = x.numel() // Cin
         dx = torch.empty_like(x)
-        dst = ctx.step.claim(Wt, b, gamma, beta) if ctx.step is not None else None
-        dW, db, dg, dbeta = dst if dst is not None else (torch.empty_like(Wt), torch.empty_like(b), torch.empty_like(gamma),
-                                                         torch.empty_like(gamma))
+        (dW, db, dg, dbeta), _, ret = _param_dsts(ctx.step, Wt, b, gamma, beta)       # (this kernel reduces them itself)
         L = _L()
         nb = L.modet_proj_ln_bwd_ws_bytes(N, Cin, dim)
         ws = _ws(nb, x)
         with _Guard(x, f"proj_ln_bwd[{Cin}->{dim}]", N * (6.0 * Cin * dim + 20.0 * dim), 4.0 * N * (2 * Cin + dim)):
-            _lib.check(L.modet_proj_ln_bwd(_p(x), _p(Wt), _p(b), _p(gamma), _p(dy), _p(dx), _p(dW), _p(db), _p(dg),
-                                           _p(dbeta), _p(ws), nb, N, Cin, dim, ctx.eps, _stream()), "modet_proj_ln_bwd")
-        if dst is not None:
-            return dx, None, None, None, None, None
-        return dx, dW, db, dg, dbeta, None
+            _call(L.modet_proj_ln_bwd, _p(x), _p(Wt), _p(b), _p(gamma), _p(dy), _p(dx), _p(dW), _p(db), _p(dg), _p(dbeta), _p(ws), nb,
+                  N, Cin, dim, ctx.eps, _stream())
+        return (dx, *ret, None)
 
 
 class _ProjLNPair(Function):
@@ -1121,8 +1159,8 @@ class _ProjLNPair(Function):
         L = _L()
         ys = [torch.empty(x.shape[:-1] + (dim,), dtype=torch.float32, device=x.device) for x in (x1, x2)]
         with _Guard(x1, f"proj_ln_fwd[{Cin}->{dim}]", 2 * N * (2.0 * Cin * dim + 8.0 * dim), 8.0 * N * (Cin + dim)):
-            _lib.check(L.modet_proj_ln_fwd_pair(_p(x1), _p(x2), _p(Wt), _p(b), _p(gamma), _p(beta), _p(ys[0]), _p(ys[1]), N, Cin, dim,
-                                                eps, _stream()), "modet_proj_ln_fwd_pair")
+            _call(L.modet_proj_ln_fwd_pair, _p(x1), _p(x2), _p(Wt), _p(b), _p(gamma), _p(beta), _p(ys[0]), _p(ys[1]), N, Cin, dim, eps,
+                  _stream())
         ctx.save_for_backward(x1, x2, Wt, b, gamma, beta)
         ctx.eps = eps
         ctx.step = current_step()
@@ -1132,27 +1170,9 @@ class _ProjLNPair(Function):
     def backward(ctx, dy1, dy2):
         x1, x2, Wt, b, gamma, beta = ctx.saved_tensors
         dy1, dy2 = dy1.contiguous(), dy2.contiguous()
-        Cin = x1.shape[-1]
-        dim = Wt.shape[0]
-        N = x1.numel() // Cin
-        dx1, dx2 = torch.empty_like(x1), torch.empty_like(x2)
-        dst = ctx.step.claim(Wt, b, gamma, beta) if ctx.step is not None else None
-        dW, db, dg, dbeta = dst if dst is not None else (torch.empty_like(Wt), torch.empty_like(b), torch.empty_like(gamma),
-                                                         torch.empty_like(gamma))
-        L = _L()
-        nb = L.modet_proj_ln_bwd_pair_ws_bytes(N, Cin, dim)
-        ws = _ws(nb, x1)
-        later = dst is not None and DEFER_LEAF_REDUCTIONS
-        out4 = (None, None, None, None) if later else (dW, db, dg, dbeta)
-        with _Guard(x1, f"proj_ln_bwd[{Cin}->{dim}]", 2 * N * (6.0 * Cin * dim + 20.0 * dim), 8.0 * N * (2 * Cin + dim)):
-            _lib.check(L.modet_proj_ln_bwd_pair(_p(x1), _p(dy1), _p(dx1), _p(x2), _p(dy2), _p(dx2), _p(Wt), _p(b), _p(gamma),
-                                                _p(out4[0]), _p(out4[1]), _p(out4[2]), _p(out4[3]), _p(ws), nb, N, Cin, dim, ctx.eps,
-                                                _stream()), "modet_proj_ln_bwd_pair")
-        if later:
-            _defer_proj(ctx.step, ws, N, Cin, dim, dW, db, dg, dbeta)
-        if dst is not None:
-            return dx1, dx2, None, None, None, None, None
-        return dx1, dx2, dW, db, dg, dbeta, None
+        dsts, later, ret = _param_dsts(ctx.step, Wt, b, gamma, beta)
+        dx1, dx2 = _proj_pair_bwd(x1, dy1, x2, dy2, Wt, b, gamma, ctx.eps, ctx.step, dsts, later)
+        return (dx1, dx2, *ret, None)
 
 
 def proj_ln_pair(x1, x2, Wt, b, gamma, beta, eps=1e-5):
@@ -1188,17 +1208,11 @@ class _NA(Function):
         _chk(q, k, rpb)
         if q.dim() != 5:
             raise RuntimeError(f"neighbourhood attention: expects channels-last (B,D,H,W,heads*head_dim) q and k, got {tuple(q.shape)}")
-        B, D, H, W, C = q.shape
         if k.shape != q.shape:
             raise RuntimeError("neighbourhood attention: q and k shapes differ")
-        hd = _na_args("neighbourhood attention", C, heads, rpb, False)
-        out = torch.empty((B, D, H, W, heads * 3), dtype=torch.float32, device=q.device)
+        _na_args("neighbourhood attention", q.shape[-1], heads, rpb, False)
         need_grad = any(ctx.needs_input_grad[:3])
-        lse = torch.empty((B, D, H, W, heads), dtype=torch.float32, device=q.device) if need_grad else None
-        nvh = float(B) * D * H * W * heads      # 60 B and ~620 flop per voxel-head
-        with _Guard(q, f"na_fwd[h{heads}]", 620.0 * nvh, 60.0 * nvh):
-            _lib.check(_L().modet_na_fwd(_p(q), _p(k), _p(rpb), _p(out), _p(lse), B, D, H, W, heads, hd, float(scale),
-                                         _stream()), "modet_na_fwd")
+        out, lse = _na_fwd(q, k, rpb, heads, scale, need_grad)
         if need_grad:
             ctx.save_for_backward(q, k, rpb, out, lse)
         ctx.heads, ctx.scale = heads, float(scale)
@@ -1208,23 +1222,9 @@ class _NA(Function):
     @staticmethod
     def backward(ctx, dout):
         q, k, rpb, out, lse = ctx.saved_tensors
-        dout = dout.contiguous()
-        B, D, H, W, C = q.shape
-        heads = ctx.heads
-        dq, dk = torch.empty_like(q), torch.empty_like(k)
-        dst = ctx.step.claim(rpb) if ctx.step is not None else None
-        drpb = dst[0] if dst is not None else torch.empty_like(rpb)
-        L = _L()
-        nb = L.modet_na_bwd_ws_bytes(B, D, H, W, heads)
-        ws = _ws(nb, q)
-        nvh = float(B) * D * H * W * heads      # reads q,k,d_out,out,lse (19 floats), writes d_q,d_k (12)
-        later = dst is not None and DEFER_LEAF_REDUCTIONS
-        with _Guard(q, f"na_bwd[h{heads}]", 1900.0 * nvh, 124.0 * nvh):
-            _lib.check(L.modet_na_bwd(_p(q), _p(k), _p(rpb), _p(out), _p(lse), _p(dout), _p(dq), _p(dk), _p(None if later else drpb),
-                                      _p(ws), nb, B, D, H, W, heads, C // heads, ctx.scale, _stream()), "modet_na_bwd")
-        if later:
-            _defer_rpb(ctx.step, ws, B, D, H, W, heads, C // heads, drpb)
-        return dq, dk, (None if dst is not None else drpb), None, None
+        (drpb,), later, ret = _param_dsts(ctx.step, rpb)
+        dq, dk = _na_bwd(q, k, rpb, out, lse, dout.contiguous(), ctx.heads, ctx.scale, ctx.step, drpb, later)
+        return dq, dk, ret[0], None, None
 
 
 class _LevelAttnBF16(Function):
@@ -1266,7 +1266,7 @@ class _LevelAttnBF16(Function):
             _chk(flow)
             Mw = torch.empty(M.shape, dtype=torch.bfloat16, device=M.device)
             with _Guard(M, f"warp_fwd[C{Cin}]", n * (24.0 * Cin + 30.0), n * ((2.0 if m16 else 4.0) * Cin + 2.0 * Cin + 12.0)):
-                _lib.check(L.modet_warp_fwd_t(_p(Md), m16, _p(flow), _p(Mw), 1, B, D, H, W, Cin, _stream()), "modet_warp_fwd_t")
+                _call(L.modet_warp_fwd_t, _p(Md), m16, _p(flow), _p(Mw), 1, B, D, H, W, Cin, _stream())
         else:
             Mw = Md
         q = torch.empty((B, D, H, W, dim), dtype=torch.bfloat16, device=F.device)
@@ -1274,15 +1274,9 @@ class _LevelAttnBF16(Function):
         for x, y in ((Fd, q), (Mw, k)):
             x16 = int(x.dtype == torch.bfloat16)
             with _Guard(F, f"proj_ln_fwd[{Cin}->{dim}]", n * (2.0 * Cin * dim + 8.0 * dim), n * ((2.0 if x16 else 4.0) * Cin + 2.0 * dim)):
-                _lib.check(L.modet_proj_ln_fwd_t(_p(x), x16, _p(Wt), _p(b), _p(gamma), _p(beta), _p(y), 1, N, Cin, dim, eps, _stream()),
-                           "modet_proj_ln_fwd_t")
-        out = torch.empty((B, D, H, W, heads * 3), dtype=torch.float32, device=F.device)
+                _call(L.modet_proj_ln_fwd_t, _p(x), x16, _p(Wt), _p(b), _p(gamma), _p(beta), _p(y), 1, N, Cin, dim, eps, _stream())
         need_grad = any(ctx.needs_input_grad)
-        lse = torch.empty((B, D, H, W, heads), dtype=torch.float32, device=F.device) if need_grad else None
-        nvh = n * heads
-        with _Guard(F, f"na_fwd[h{heads}]", 620.0 * nvh, 36.0 * nvh):
-            _lib.check(L.modet_na_fwd_t(_p(q), _p(k), 1, _p(rpb), _p(out), _p(lse), B, D, H, W, heads, dim // heads, float(scale),
-                                        _stream()), "modet_na_fwd_t")
+        out, lse = _na_fwd(q, k, rpb, heads, scale, need_grad)
         if need_grad:
             ctx.save_for_backward(Fd, Md, flow, Mw if flow is not None else None, q, k, Wt, b, gamma, rpb, out, lse)
         ctx.heads, ctx.scale, ctx.eps = heads, float(scale), eps
@@ -1297,55 +1291,16 @@ class _LevelAttnBF16(Function):
             return None, None, galias, None, None, None, None, None, None, None, None, None
         dout = dout.contiguous()
         galias = None if galias is None else galias.contiguous()
-        B, D, H, W, Cin = F.shape
-        dim = Wt.shape[0]
-        heads = ctx.heads
-        N = B * D * H * W
-        n = float(N)
-        L = _L()
-        dq = torch.empty((B, D, H, W, dim), dtype=torch.float32, device=F.device)
-        dk = torch.empty_like(dq)
         # the five parameter gradients straight into the flat gradient buffer when a deferred() scope offers destinations
-        dst = ctx.step.claim(Wt, b, gamma, ctx.beta_ref, rpb) if ctx.step is not None else None
-        drpb = dst[4] if dst is not None else torch.empty_like(rpb)
-        nb = L.modet_na_bwd_ws_bytes(B, D, H, W, heads)
-        ws = _ws(nb, F)
-        nvh = n * heads
-        later = dst is not None and DEFER_LEAF_REDUCTIONS
-        with _Guard(F, f"na_bwd[h{heads}]", 1900.0 * nvh, 100.0 * nvh):
-            _lib.check(L.modet_na_bwd_t(_p(q), _p(k), 1, _p(rpb), _p(out), _p(lse), _p(dout), _p(dq), _p(dk), _p(None if later else drpb),
-                                        _p(ws), nb, B, D, H, W, heads, dim // heads, ctx.scale, _stream()), "modet_na_bwd_t")
-        if later:
-            _defer_rpb(ctx.step, ws, B, D, H, W, heads, dim // heads, drpb)
-        x2 = Mw if flow is not None else M
-        dF = torch.empty(F.shape, dtype=torch.float32, device=F.device)
-        dMw = torch.empty(M.shape, dtype=torch.float32, device=M.device)
-        dW, db, dg, dbeta = dst[:4] if dst is not None else (torch.empty_like(Wt), torch.empty_like(b), torch.empty_like(gamma),
-                                                             torch.empty_like(gamma))
-        nb2 = L.modet_proj_ln_bwd_pair_ws_bytes(N, Cin, dim)
-        if nb2 == 0:
-            raise RuntimeError(f"level attention (bf16): no paired projection backward for Cin {Cin}, dim {dim}")
-        ws2 = _ws(nb2, F)
-        with _Guard(F, f"proj_ln_bwd[{Cin}->{dim}]", 2 * n * (6.0 * Cin * dim + 20.0 * dim), n * (14.0 * Cin + 8.0 * dim)):
-            out4 = (None, None, None, None) if later else (dW, db, dg, dbeta)
-            _lib.check(L.modet_proj_ln_bwd_pair_t(_p(F), int(F.dtype == torch.bfloat16), _p(dq), _p(dF), _p(x2),
-                                                  int(x2.dtype == torch.bfloat16), _p(dk), _p(dMw),
-                                                  _p(Wt), _p(b), _p(gamma), _p(out4[0]), _p(out4[1]), _p(out4[2]), _p(out4[3]), _p(ws2),
-                                                  nb2, N, Cin, dim, ctx.eps, _stream()), "modet_proj_ln_bwd_pair_t")
-        if later:
-            _defer_proj(ctx.step, ws2, N, Cin, dim, dW, db, dg, dbeta)
-        if dst is not None:
-            dW = db = dg = dbeta = drpb = None           # (written in place: nothing for autograd to hand on)
+        dsts, later, ret = _param_dsts(ctx.step, Wt, b, gamma, ctx.beta_ref, rpb)
+        dq, dk = _na_bwd(q, k, rpb, out, lse, dout, ctx.heads, ctx.scale, ctx.step, dsts[4], later)
+        dF, dMw = _proj_pair_bwd(F, dq, Mw if flow is not None else M, dk, Wt, b, gamma, ctx.eps, ctx.step, dsts[:4], later, typed=True)
         if flow is None:
-            return dF, dMw, None, dW, db, dg, dbeta, drpb, None, None, None, None
-        dM = torch.empty(M.shape, dtype=torch.float32, device=M.device) if ctx.needs_input_grad[1] else None
-        dflow = torch.empty_like(flow) if ctx.needs_input_grad[2] else None
-        if dM is not None or dflow is not None:
-            with _Guard(M, _warp_bwd_tag(M, dM, 0, 0), n * (60.0 * Cin + 40.0), 4.0 * n * (3 * Cin + 6)):
-                _warp_backward(M, flow, dMw, dM, dflow, galias, 0, 0)
-        elif galias is not None:
-            dflow = galias
-        return dF, dM, dflow, dW, db, dg, dbeta, drpb, None, None, None, None
+            return (dF, dMw, None, *ret, None, None, None, None)
+        dM, dflow = None, galias
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dM, dflow = _warp_bwd(M, flow, dMw, ctx.needs_input_grad[1], ctx.needs_input_grad[2], galias)
+        return (dF, dM, dflow, *ret, None, None, None, None)
 
 
 def level_attention_bf16(F, M, flow, Wt, b, gamma, beta, rpb, heads, scale, eps=1e-5, tee=False):
@@ -1371,7 +1326,7 @@ class _Corr3d(Function):
         ws = _ws(nb, mov)
         n = float(B) * D * H * W
         with _Guard(mov, f"corr3d_fwd[C{C}]", n * C * (54.0 + 54.0), 4.0 * n * (2 * C + 27)):
-            _lib.check(L.modet_corr3d_fwd(_p(mov), _p(fix), _p(corr), _p(ws), nb, B, D, H, W, C, _stream()), "modet_corr3d_fwd")
+            _call(L.modet_corr3d_fwd, _p(mov), _p(fix), _p(corr), _p(ws), nb, B, D, H, W, C, _stream())
         ctx.save_for_backward(mov, fix)
         return corr
 
@@ -1386,8 +1341,7 @@ class _Corr3d(Function):
         ws = _ws(nb, mov)
         n = float(B) * D * H * W
         with _Guard(mov, f"corr3d_bwd[C{C}]", n * C * 4 * 54.0, 4.0 * n * (4 * C + 27)):
-            _lib.check(L.modet_corr3d_bwd(_p(mov), _p(fix), _p(dcorr), _p(dmov), _p(dfix), _p(ws), nb, B, D, H, W, C,
-                                          _stream()), "modet_corr3d_bwd")
+            _call(L.modet_corr3d_bwd, _p(mov), _p(fix), _p(dcorr), _p(dmov), _p(dfix), _p(ws), nb, B, D, H, W, C, _stream())
         return dmov, dfix
 
 
@@ -1401,19 +1355,24 @@ def neighbourhood_attention(q, k, rpb, heads, scale):
     return _NA.apply(q, k, rpb.contiguous(), heads, scale)
 
 
+def _warp_fwd(src, flow, mode=0, add_flow=0):
+    """THE fp32 warp forward launch, with its argument checks"""
+    _chk(src, flow)
+    _rank5("warp", "src", src)
+    B, D, H, W, C = src.shape
+    if tuple(flow.shape) != (B, D, H, W, 3):
+        raise RuntimeError(f"warp: flow {tuple(flow.shape)} does not match src {tuple(src.shape)}")
+    out = torch.empty_like(src)
+    n = float(B) * D * H * W                # 4*(2C+3) B per voxel (SURVEY.md §8d)
+    with _Guard(src, f"warp_fwd[C{C}]", n * (24.0 * C + 30.0), 4.0 * n * (2 * C + 3)):
+        _call(_L().modet_warp_fwd, _p(src), _p(flow), _p(out), B, D, H, W, C, mode, int(add_flow), _stream())
+    return out
+
+
 class _Warp(Function):
     @staticmethod
     def forward(ctx, src, flow, mode, add_flow, flow_bound=0):
-        _chk(src, flow)
-        _rank5("warp", "src", src)
-        B, D, H, W, C = src.shape
-        if tuple(flow.shape) != (B, D, H, W, 3):
-            raise RuntimeError(f"warp: flow {tuple(flow.shape)} does not match src {tuple(src.shape)}")
-        out = torch.empty_like(src)
-        n = float(B) * D * H * W                # 4*(2C+3) B per voxel
-        with _Guard(src, f"warp_fwd[C{C}]", n * (24.0 * C + 30.0), 4.0 * n * (2 * C + 3)):
-            _lib.check(_L().modet_warp_fwd(_p(src), _p(flow), _p(out), B, D, H, W, C, mode, int(add_flow), _stream()),
-                       "modet_warp_fwd")
+        out = _warp_fwd(src, flow, mode, add_flow)
         ctx.save_for_backward(src, flow)
         ctx.mode, ctx.add_flow, ctx.flow_bound = mode, int(add_flow), int(flow_bound)
         return out
@@ -1423,14 +1382,8 @@ class _Warp(Function):
         src, flow = ctx.saved_tensors
         if ctx.mode != 0:
             raise RuntimeError("warp: nearest mode is not differentiable")
-        dout = dout.contiguous()
-        B, D, H, W, C = src.shape
-        dsrc = torch.empty_like(src) if ctx.needs_input_grad[0] else None
-        dflow = torch.empty_like(flow) if ctx.needs_input_grad[1] else None
-        n = float(B) * D * H * W
-        tag = _warp_bwd_tag(src, dsrc, ctx.add_flow, ctx.flow_bound if C == 3 else 0)     # the kernels that run
-        with _Guard(src, tag, n * (60.0 * C + 40.0), 4.0 * n * (3 * C + 6)):
-            _warp_backward(src, flow, dout, dsrc, dflow, None, ctx.add_flow, ctx.flow_bound if C == 3 else 0)
+        dsrc, dflow = _warp_bwd(src, flow, dout.contiguous(), ctx.needs_input_grad[0], ctx.needs_input_grad[1], None, ctx.add_flow,
+                                ctx.flow_bound if src.shape[-1] == 3 else 0)
         return dsrc, dflow, None, None, None
 
 
@@ -1455,48 +1408,70 @@ def set_deterministic(on=True):
 WARP_TILES = True
 
 
-def _warp_bwd_tag(src, dsrc, add_flow, flow_bound):
+def _warp_bwd_kind(src, dout, dsrc, add_flow, flow_bound):
+    """THE choice of a warp backward's kernels, for the launch and for its tag -> (kind, workspace bytes):
+    'tiles'  destination tiles (feature warps: C % 8 == 0, and the fp32 C == 3 warps; d_src wanted, fp32 d_out)
+    'det'    deterministic mode, d_src of another channel count: 64-bit integer atomics on global memory
+    'acc'    the float-atomic kernel -- with flow_bound (C == 3) its d_src is a gather without atomics"""
+    B, D, H, W, C = src.shape
+    if dsrc is not None and not flow_bound:
+        if (WARP_TILES and (C == 3 or not add_flow) and not (C == 3 and src.dtype == torch.bfloat16)
+                and dout.dtype == torch.float32):
+            nb = _L().modet_warp_bwd_dsrc_tiles_ws_bytes(B, D, H, W, C)
+            if nb:
+                return "tiles", nb
+        if DETERMINISTIC:
+            return "det", _L().modet_warp_bwd_det_ws_bytes(B, D, H, W, C)
+    return "acc", 0
+
+
+def _warp_bwd_tag(src, dout, dsrc, add_flow, flow_bound):
     """launch tag of a warp backward = the kernels that run (bench.py maps tags to kernel families); like _conv_tag only
     evaluated while a timer is installed"""
     if _TIMER is None:
         return None
-    B, D, H, W, C = src.shape
-    if C == 3 and flow_bound:
-        return "warp_bwd_gather3[C3]"
-    s16 = src.dtype == torch.bfloat16
-    if (WARP_TILES and dsrc is not None and (C == 3 or not add_flow) and not (C == 3 and s16)
-            and _L().modet_warp_bwd_dsrc_tiles_ws_bytes(B, D, H, W, C)):
+    C = src.shape[-1]
+    kind, _ = _warp_bwd_kind(src, dout, dsrc, add_flow, flow_bound)
+    if kind == "tiles":
         return f"warp_bwd_tiles[C{C}]"
-    return f"warp_bwd[C{C}]"
+    return "warp_bwd_gather3[C3]" if C == 3 and flow_bound else f"warp_bwd[C{C}]"
 
 
 def _warp_backward(src, flow, dout, dsrc, dflow, galias, add_flow, flow_bound):
-    """launch the warp backward: destination tiles (feature warps: C % 8 == 0, d_src wanted), else the float-atomic / gather
-    kernel, else (deterministic mode, d_src of another channel count) 64-bit integer atomics on global memory.
-    galias = a second flow gradient added on the way out"""
+    """launch the warp backward _warp_bwd_kind chooses; galias = a second flow gradient added on the way out"""
     B, D, H, W, C = src.shape
     L = _L()
-    s16 = int(src.dtype == torch.bfloat16)
-    if (WARP_TILES and dsrc is not None and not flow_bound and (C == 3 or not add_flow) and not (C == 3 and s16)
-            and dout.dtype == torch.float32):
-        nb = L.modet_warp_bwd_dsrc_tiles_ws_bytes(B, D, H, W, C)
-        if nb:
-            ws = _ws(nb, src)
-            if dflow is not None:
-                _lib.check(L.modet_warp_bwd_tiles(_p(src), s16, _p(flow), _p(dout), _p(dsrc), _p(dflow), _p(galias), _p(ws), nb,
-                                                  B, D, H, W, C, int(add_flow), _stream()), "modet_warp_bwd_tiles")
-            else:
-                _lib.check(L.modet_warp_bwd_dsrc_tiles(_p(flow), _p(dout), _p(dsrc), _p(ws), nb, B, D, H, W, C, _stream()),
-                           "modet_warp_bwd_dsrc_tiles")
-            return
-    if DETERMINISTIC and dsrc is not None and not flow_bound:
-        nb = L.modet_warp_bwd_det_ws_bytes(B, D, H, W, C)
-        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=src.device)
-        _lib.check(L.modet_warp_bwd_det(_p(src), s16, _p(flow), _p(dout), _p(dsrc), _p(dflow), _p(galias if dflow is not None else None),
-                                        _p(ws), nb, B, D, H, W, C, int(add_flow), _stream()), "modet_warp_bwd_det")
+    s16 = _isbf(src)
+    kind, nb = _warp_bwd_kind(src, dout, dsrc, add_flow, flow_bound)
+    if kind == "tiles":
+        ws = _ws(nb, src)
+        if dflow is not None:
+            _call(L.modet_warp_bwd_tiles, _p(src), s16, _p(flow), _p(dout), _p(dsrc), _p(dflow), _p(galias), _p(ws), nb, B, D, H, W, C,
+                  int(add_flow), _stream())
+        else:
+            _call(L.modet_warp_bwd_dsrc_tiles, _p(flow), _p(dout), _p(dsrc), _p(ws), nb, B, D, H, W, C, _stream())
         return
-    _lib.check(L.modet_warp_bwd_acc(_p(src), s16, _p(flow), _p(dout), _p(dsrc), _p(dflow), _p(galias if dflow is not None else None),
-                                    B, D, H, W, C, int(add_flow), int(flow_bound), _stream()), "modet_warp_bwd_acc")
+    galias = galias if dflow is not None else None
+    if kind == "det":
+        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=src.device)
+        _call(L.modet_warp_bwd_det, _p(src), s16, _p(flow), _p(dout), _p(dsrc), _p(dflow), _p(galias), _p(ws), nb, B, D, H, W, C,
+              int(add_flow), _stream())
+        return
+    _call(L.modet_warp_bwd_acc, _p(src), s16, _p(flow), _p(dout), _p(dsrc), _p(dflow), _p(galias), B, D, H, W, C, int(add_flow),
+          int(flow_bound), _stream())
+
+
+def _warp_bwd(src, flow, dout, want_src, want_flow, galias=None, add_flow=0, flow_bound=0, alias_counted=False):
+    """THE bracket of a warp backward: gradient buffers, tag, figures and launch -> (d_src, d_flow), each None when not wanted.
+    alias_counted: the byte figure includes reading galias (_WarpTee's does, the level node's never did)"""
+    B, D, H, W, C = src.shape
+    dsrc = torch.empty(src.shape, dtype=torch.float32, device=src.device) if want_src else None
+    dflow = torch.empty_like(flow) if want_flow else None
+    n = float(B) * D * H * W
+    with _Guard(src, _warp_bwd_tag(src, dout, dsrc, add_flow, flow_bound), n * (60.0 * C + 40.0),
+                4.0 * n * (3 * C + 6 + (3 if alias_counted and galias is not None else 0))):
+        _warp_backward(src, flow, dout, dsrc, dflow, galias, add_flow, flow_bound)
+    return dsrc, dflow
 
 
 class _WarpTee(Function):
@@ -1507,15 +1482,7 @@ class _WarpTee(Function):
 
     @staticmethod
     def forward(ctx, src, flow):
-        _chk(src, flow)
-        _rank5("warp", "src", src)
-        B, D, H, W, C = src.shape
-        if tuple(flow.shape) != (B, D, H, W, 3):
-            raise RuntimeError(f"warp: flow {tuple(flow.shape)} does not match src {tuple(src.shape)}")
-        out = torch.empty_like(src)
-        n = float(B) * D * H * W
-        with _Guard(src, f"warp_fwd[C{C}]", n * (24.0 * C + 30.0), 4.0 * n * (2 * C + 3)):
-            _lib.check(_L().modet_warp_fwd(_p(src), _p(flow), _p(out), B, D, H, W, C, 0, 0, _stream()), "modet_warp_fwd")
+        out = _warp_fwd(src, flow)
         ctx.save_for_backward(src, flow)
         ctx.set_materialize_grads(False)
         return out, flow.view_as(flow)
@@ -1527,13 +1494,7 @@ class _WarpTee(Function):
             return None, galias
         dout = dout.contiguous()
         galias = None if galias is None else galias.contiguous()
-        B, D, H, W, C = src.shape
-        dsrc = torch.empty_like(src) if ctx.needs_input_grad[0] else None
-        dflow = torch.empty_like(flow) if ctx.needs_input_grad[1] else None
-        n = float(B) * D * H * W
-        with _Guard(src, _warp_bwd_tag(src, dsrc, 0, 0), n * (60.0 * C + 40.0), 4.0 * n * (3 * C + 6 + (3 if galias is not None else 0))):
-            _warp_backward(src, flow, dout, dsrc, dflow, galias, 0, 0)
-        return dsrc, dflow
+        return _warp_bwd(src, flow, dout, ctx.needs_input_grad[0], ctx.needs_input_grad[1], galias, alias_counted=True)
 
 
 def warp_tee(src, flow):
@@ -1565,8 +1526,7 @@ class _Upsample2(Function):
         B, d, h, w, C = x.shape
         y = torch.empty((B, 2 * d, 2 * h, 2 * w, C), dtype=torch.float32, device=x.device)
         with _Guard(x, f"upsample2_fwd[C{C}]", 16.0 * y.numel(), 4.0 * (x.numel() + y.numel())):
-            _lib.check(_L().modet_upsample2_fwd(_p(x), _p(y), B, d, h, w, C, float(scale), _stream()),
-                       "modet_upsample2_fwd")
+            _call(_L().modet_upsample2_fwd, _p(x), _p(y), B, d, h, w, C, float(scale), _stream())
         ctx.shape, ctx.scale = (B, d, h, w, C), float(scale)
         return y
 
@@ -1580,11 +1540,9 @@ class _Upsample2(Function):
         ws = _ws(nb, dy) if nb else None
         with _Guard(dy, f"upsample2_bwd[C{C}]", 16.0 * dy.numel(), 4.0 * (dx.numel() + dy.numel())):
             if nb:
-                _lib.check(L.modet_upsample2_bwd_sep(_p(dy), _p(dx), _p(ws), nb, B, d, h, w, C, ctx.scale, _stream()),
-                           "modet_upsample2_bwd_sep")
+                _call(L.modet_upsample2_bwd_sep, _p(dy), _p(dx), _p(ws), nb, B, d, h, w, C, ctx.scale, _stream())
             else:
-                _lib.check(L.modet_upsample2_bwd(_p(dy), _p(dx), B, d, h, w, C, ctx.scale, _stream()),
-                           "modet_upsample2_bwd")
+                _call(L.modet_upsample2_bwd, _p(dy), _p(dx), B, d, h, w, C, ctx.scale, _stream())
         return dx, None
 
 
@@ -1602,7 +1560,7 @@ class _CwmTail(Function):
         N = logits.numel() // heads
         out = torch.empty(logits.shape[:-1] + (3,), dtype=torch.float32, device=x.device)
         with _Guard(x, "cwm_tail_fwd", 12.0 * x.numel(), 4.0 * (x.numel() + logits.numel() + out.numel())):
-            _lib.check(_L().modet_cwm_tail_fwd(_p(x), _p(logits), _p(out), N, heads, _stream()), "modet_cwm_tail_fwd")
+            _call(_L().modet_cwm_tail_fwd, _p(x), _p(logits), _p(out), N, heads, _stream())
         ctx.save_for_backward(x, logits)
         return out
 
@@ -1614,8 +1572,7 @@ class _CwmTail(Function):
         N = logits.numel() // heads
         dx, dl = torch.empty_like(x), torch.empty_like(logits)
         with _Guard(x, "cwm_tail_bwd", 20.0 * x.numel(), 8.0 * (x.numel() + logits.numel()) + 4.0 * dout.numel()):
-            _lib.check(_L().modet_cwm_tail_bwd(_p(x), _p(logits), _p(dout), _p(dx), _p(dl), N, heads, _stream()),
-                       "modet_cwm_tail_bwd")
+            _call(_L().modet_cwm_tail_bwd, _p(x), _p(logits), _p(dout), _p(dx), _p(dl), N, heads, _stream())
         return dx, dl
 
 
@@ -1634,7 +1591,7 @@ class _ToCL(Function):
             return x.reshape((B,) + tuple(x.shape[2:]) + (1,))
         y = torch.empty((B,) + tuple(x.shape[2:]) + (C,), dtype=torch.float32, device=x.device)
         with _Guard(x, "layout", 0.0, 8.0 * x.numel()):
-            _lib.check(_L().modet_ncdhw_to_cl(_p(x), _p(y), B, C, V, _stream()), "modet_ncdhw_to_cl")
+            _call(_L().modet_ncdhw_to_cl, _p(x), _p(y), B, C, V, _stream())
         return y
 
     @staticmethod
@@ -1652,7 +1609,7 @@ class _ToNCDHW(Function):
             return x.reshape((B, 1) + tuple(x.shape[1:-1]))
         y = torch.empty((B, C) + tuple(x.shape[1:-1]), dtype=torch.float32, device=x.device)
         with _Guard(x, "layout", 0.0, 8.0 * x.numel()):
-            _lib.check(_L().modet_cl_to_ncdhw(_p(x), _p(y), B, C, V, _stream()), "modet_cl_to_ncdhw")
+            _call(_L().modet_cl_to_ncdhw, _p(x), _p(y), B, C, V, _stream())
         return y
 
     @staticmethod
@@ -1673,8 +1630,7 @@ def to_ncdhw(x):
 def _scale_by(x, s):
     y = torch.empty_like(x)
     with _Guard(x, "scale", x.numel(), 8.0 * x.numel()):
-        _lib.check(_L().modet_scale_by_dev_scalar(_p(x), _p(s), _p(y), x.numel(), _stream()),
-                   "modet_scale_by_dev_scalar")
+        _call(_L().modet_scale_by_dev_scalar, _p(x), _p(s), _p(y), x.numel(), _stream())
     return y
 
 
@@ -1693,15 +1649,13 @@ def _ncc_launch(I, J, want_grad, win=9):
         ws = _ws(nb, I)
         nv = float(I.numel())
         with _Guard(I, "ncc_fwd_bwd_box", 30.0 * (wz + wy + wx) * nv, 150.0 * nv):
-            _lib.check(L.modet_ncc_fwd_bwd_box(_p(I), _p(J), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, wz, wy, wx, _stream()),
-                       "modet_ncc_fwd_bwd_box")
+            _call(L.modet_ncc_fwd_bwd_box, _p(I), _p(J), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, wz, wy, wx, _stream())
         return loss, dJ
     nb = L.modet_ncc_ws_bytes(B, D, H, W)
     ws = _ws(nb, I)
     nv = float(I.numel())               # reads I,J once, writes d_J once
     with _Guard(I, "ncc_fwd_bwd", 400.0 * nv, 12.0 * nv):
-        _lib.check(L.modet_ncc_fwd_bwd_win(_p(I), _p(J), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, int(win), _stream()),
-                   "modet_ncc_fwd_bwd_win")
+        _call(L.modet_ncc_fwd_bwd_win, _p(I), _p(J), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, int(win), _stream())
     return loss, dJ
 
 
@@ -1760,8 +1714,7 @@ class _Grad3d(Function):
         nb = L.modet_grad3d_ws_bytes(B, D, H, W)
         ws = _ws(nb, flow)
         with _Guard(flow, "grad3d_fwd_bwd", 20.0 * flow.numel(), 8.0 * flow.numel()):
-            _lib.check(L.modet_grad3d_fwd_bwd(_p(flow), _p(loss), _p(df), _p(ws), nb, B, D, H, W, int(penalty), _stream()),
-                       "modet_grad3d_fwd_bwd")
+            _call(L.modet_grad3d_fwd_bwd, _p(flow), _p(loss), _p(df), _p(ws), nb, B, D, H, W, int(penalty), _stream())
         ctx.save_for_backward(df)
         return loss.reshape(())
 
@@ -1806,7 +1759,7 @@ def mind_ssc(img, radius=2, dilation=2):
     ws = _ws(nb, img)
     nv = float(img.numel())
     with _Guard(img, "mind_descriptor", 600.0 * nv, 148.0 * nv):
-        _lib.check(L.modet_mind_descriptor(_p(img), _p(out), _p(ws), nb, B, D, H, W, 2, 2, _stream()), "modet_mind_descriptor")
+        _call(L.modet_mind_descriptor, _p(img), _p(out), _p(ws), nb, B, D, H, W, 2, 2, _stream())
     return out
 
 
@@ -1822,8 +1775,7 @@ def _mind_launch(a, b, want_grad, grad_scale=1.0):
     ws = _ws(nb, a)
     nv = float(a.numel())
     with _Guard(a, "mind_fwd_bwd", 1500.0 * nv, (MIND_BYTES_PER_VOXEL if want_grad else 200.0) * nv):
-        _lib.check(L.modet_mind_fwd_bwd(_p(a), _p(b), _p(loss), _p(d_b), _p(ws), nb, B, D, H, W, 2, 2, float(grad_scale), _stream()),
-                   "modet_mind_fwd_bwd")
+        _call(L.modet_mind_fwd_bwd, _p(a), _p(b), _p(loss), _p(d_b), _p(ws), nb, B, D, H, W, 2, 2, float(grad_scale), _stream())
     return loss, d_b
 
 
@@ -1873,8 +1825,8 @@ def ncc_value_and_grad(y_true, y_pred, win=9, grad_scale=1.0):
     ws = _ws(nb, y_true)
     nv = float(y_true.numel())
     with _Guard(y_true, "ncc_fwd_bwd", 400.0 * nv, 12.0 * nv):
-        _lib.check(L.modet_ncc_fwd_bwd_win_scaled(_p(y_true), _p(y_pred), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, int(win),
-                                                  float(grad_scale), _stream()), "modet_ncc_fwd_bwd_win_scaled")
+        _call(L.modet_ncc_fwd_bwd_win_scaled, _p(y_true), _p(y_pred), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, int(win),
+              float(grad_scale), _stream())
     return loss.reshape(()), dJ
 
 
@@ -1901,8 +1853,8 @@ def grad3d_value_and_grad_cl(flow_cl, penalty="l2", grad_scale=1.0):
     nb = L.modet_grad3d_ws_bytes(B, D, H, W)
     ws = _ws(nb, flow_cl)
     with _Guard(flow_cl, "grad3d_fwd_bwd", 20.0 * flow_cl.numel(), 8.0 * flow_cl.numel()):
-        _lib.check(L.modet_grad3d_fwd_bwd_cl(_p(flow_cl), _p(loss), _p(df), _p(ws), nb, B, D, H, W, 1 if penalty == "l1" else 2,
-                                             float(grad_scale), _stream()), "modet_grad3d_fwd_bwd_cl")
+        _call(L.modet_grad3d_fwd_bwd_cl, _p(flow_cl), _p(loss), _p(df), _p(ws), nb, B, D, H, W, 1 if penalty == "l1" else 2,
+              float(grad_scale), _stream())
     return loss.reshape(()), df
 
 
@@ -1913,9 +1865,8 @@ def adam_amsgrad_step_(p, g, m, v, vmax, lr, step, beta1=0.9, beta2=0.999, eps=1
         if t.numel() != p.numel():
             raise RuntimeError(f"adam_amsgrad_step_: {name} {tuple(t.shape)} does not match p {tuple(p.shape)}")
     with _Guard(p, "adam_amsgrad", 12.0 * p.numel(), 28.0 * p.numel()):
-        _lib.check(_L().modet_adam_amsgrad_step(_p(p), _p(g), _p(m), _p(v), _p(vmax), p.numel(), float(lr), beta1,
-                                                beta2, eps, int(step), float(grad_scale), _stream()),
-                   "modet_adam_amsgrad_step")
+        _call(_L().modet_adam_amsgrad_step, _p(p), _p(g), _p(m), _p(v), _p(vmax), p.numel(), float(lr), beta1, beta2, eps, int(step),
+              float(grad_scale), _stream())
 
 
 def label_warp_counts(lab_moving, flow_cl, lab_fixed, nlabels=54, want_warped=True):
@@ -1939,8 +1890,7 @@ def label_warp_counts(lab_moving, flow_cl, lab_fixed, nlabels=54, want_warped=Tr
     warped = torch.empty((D, H, W), dtype=torch.int16, device=lm.device) if want_warped else None
     counts = torch.empty((3, nlabels + 1), dtype=torch.int64, device=lm.device)
     with _Guard(flow_cl):
-        _lib.check(_L().modet_label_warp_counts(_p(lm), _p(flow_cl), _p(lf), _p(warped), _p(counts), D, H, W, nlabels,
-                                                _stream()), "modet_label_warp_counts")
+        _call(_L().modet_label_warp_counts, _p(lm), _p(flow_cl), _p(lf), _p(warped), _p(counts), D, H, W, nlabels, _stream())
     return warped, counts
 
 
@@ -1957,8 +1907,7 @@ def jacdet_nonpos_count(flow_cl, want_det=False):
     counts = torch.empty(B, dtype=torch.int64, device=flow_cl.device)
     det = torch.empty((B, D, H, W), dtype=torch.float64, device=flow_cl.device) if want_det else None
     with _Guard(flow_cl, "jacdet", 60.0 * flow_cl.numel() / 3, 4.0 * flow_cl.numel()):
-        _lib.check(_L().modet_jacdet_nonpos_count(_p(flow_cl), _p(counts), _p(det), B, D, H, W, _stream()),
-                   "modet_jacdet_nonpos_count")
+        _call(_L().modet_jacdet_nonpos_count, _p(flow_cl), _p(counts), _p(det), B, D, H, W, _stream())
     return counts, det
 
 
@@ -1987,7 +1936,7 @@ def cast_bf16(x, to_bf16):
     _chk16(x)
     y = torch.empty(x.shape, dtype=torch.bfloat16 if to_bf16 else torch.float32, device=x.device)
     with _Guard(x, "cast_bf16", 0.0, 6.0 * x.numel()):
-        _lib.check(_L().modet_cast_bf16(_p(x), _p(y), x.numel(), int(to_bf16), _stream()), "modet_cast_bf16")
+        _call(_L().modet_cast_bf16, _p(x), _p(y), x.numel(), int(to_bf16), _stream())
     return y
 
 
@@ -2010,8 +1959,8 @@ def conv3d_bf16_forward(x, w, b, want_stats=True, step=None):
     stats = torch.empty(sb // 4, dtype=torch.float32, device=x.device) if sb > 0 else None
     n = float(B) * D * H * W
     with _Guard(x, _conv16_tag("fwd", x.shape, Cin, Cout, _isbf(x)), 54.0 * Cin * Cout * n, n * ((2.0 if _isbf(x) else 4.0) * Cin + 2.0 * Cout)):
-        _lib.check(L.modet_conv3d_bf16_fwd(_p(x), _isbf(x), _p(w), _p(b), _p(y), _p(ws), nb, _p(stats), sb, B, D, H, W, Cin, Cout,
-                                           _stream(), _h(step)), "modet_conv3d_bf16_fwd")
+        _call(L.modet_conv3d_bf16_fwd, _p(x), _isbf(x), _p(w), _p(b), _p(y), _p(ws), nb, _p(stats), sb, B, D, H, W, Cin, Cout,
+              _stream(), _h(step))
     return y, stats
 
 
@@ -2029,8 +1978,7 @@ def conv3d_bf16_backward_data(dy, w, Cin, dx_bf16, step=None):
     ws = _ws(nb, dy)
     n = float(B) * D * H * W
     with _Guard(dy, _conv16_tag("dgrad", dy.shape, Cin, Cout, True), 54.0 * Cin * Cout * n, n * (2.0 * Cout + (2.0 if dx_bf16 else 4.0) * Cin)):
-        _lib.check(L.modet_conv3d_bf16_bwd_data(_p(dy), _p(w), _p(dx), int(dx_bf16), _p(ws), nb, B, D, H, W, Cin, Cout, _stream(),
-                                                _h(step)), "modet_conv3d_bf16_bwd_data")
+        _call(L.modet_conv3d_bf16_bwd_data, _p(dy), _p(w), _p(dx), int(dx_bf16), _p(ws), nb, B, D, H, W, Cin, Cout, _stream(), _h(step))
     return dx
 
 
@@ -2043,32 +1991,32 @@ def conv3d_bf16_backward_weight(x, dy, w=None, b=None, step=None):
     if dy.dtype != torch.bfloat16:
         raise RuntimeError(f"conv3d_bf16_backward_weight: the gradient must be bfloat16, got {dy.dtype}")
     L = _L()
-    if hasattr(L, "modet_conv3d_bf16_bwd_weight"):
-        B, D, H, W, Cin = x.shape
-        Cout = dy.shape[-1]
-        nb = L.modet_conv3d_bf16_bwd_weight_ws_bytes(B, D, H, W, Cin, Cout)
-        ws = _ws(nb, x)
-        n = float(B) * D * H * W
-        scope = step if step is not None else current_step()
-        dst = scope.destinations(w, b, True) if (scope is not None and hasattr(L, "modet_conv3d_bf16_bwd_weight_defer")) else None
-        if dst is not None:
-            dw, db = dst
-            with _Guard(x, _conv16_tag("wgrad", x.shape, Cin, Cout, _isbf(x)), 54.0 * Cin * Cout * n, n * ((2.0 if _isbf(x) else 4.0) * Cin + 2.0 * Cout)):
-                _lib.check(L.modet_conv3d_bf16_bwd_weight_defer(_p(x), _isbf(x), _p(dy), _p(dw), _p(db), _p(ws), nb, B, D, H, W,
-                                                                Cin, Cout, _stream(), _h(scope)),
-                           "modet_conv3d_bf16_bwd_weight_defer")
-            scope._keep.append(ws)
-            scope.written.add(w.data_ptr())
-            scope.written.add(b.data_ptr())
-            return None, None
+    if not hasattr(L, "modet_conv3d_bf16_bwd_weight"):      # (an older library loaded through MODET_HIP_LIB for A/B timing)
+        x32 = x if x.dtype == torch.float32 else cast_bf16(x, False)
+        return conv3d_backward_weight(x32, cast_bf16(dy, False), True)
+    B, D, H, W, Cin = x.shape
+    Cout = dy.shape[-1]
+    nb = L.modet_conv3d_bf16_bwd_weight_ws_bytes(B, D, H, W, Cin, Cout)
+    ws = _ws(nb, x)
+    n = float(B) * D * H * W
+
+    def launch(fn, dw, db, *handle):
+        """the one library call: with a step-context handle the partial tiles are reduced at its flush, else now"""
+        with _Guard(x, _conv16_tag("wgrad", x.shape, Cin, Cout, _isbf(x)), 54.0 * Cin * Cout * n, n * ((2.0 if _isbf(x) else 4.0) * Cin + 2.0 * Cout)):
+            _call(fn, _p(x), _isbf(x), _p(dy), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin, Cout, _stream(), *handle)
+
+    scope = step if step is not None else current_step()
+    dst = scope.destinations(w, b, True) if (scope is not None and hasattr(L, "modet_conv3d_bf16_bwd_weight_defer")) else None
+    if dst is None:
         dw = torch.empty((Cout, Cin, 3, 3, 3), dtype=torch.float32, device=x.device)
         db = torch.empty((Cout,), dtype=torch.float32, device=x.device)
-        with _Guard(x, _conv16_tag("wgrad", x.shape, Cin, Cout, _isbf(x)), 54.0 * Cin * Cout * n, n * ((2.0 if _isbf(x) else 4.0) * Cin + 2.0 * Cout)):
-            _lib.check(L.modet_conv3d_bf16_bwd_weight(_p(x), _isbf(x), _p(dy), _p(dw), _p(db), _p(ws), nb, B, D, H, W, Cin, Cout,
-                                                      _stream()), "modet_conv3d_bf16_bwd_weight")
+        launch(L.modet_conv3d_bf16_bwd_weight, dw, db)
         return dw, db
-    x32 = x if x.dtype == torch.float32 else cast_bf16(x, False)
-    return conv3d_backward_weight(x32, cast_bf16(dy, False), True)
+    launch(L.modet_conv3d_bf16_bwd_weight_defer, *dst, _h(scope))
+    scope._keep.append(ws)
+    scope.written.add(w.data_ptr())
+    scope.written.add(b.data_ptr())
+    return None, None
 
 
 class _Conv3dBF16(Function):
@@ -2094,45 +2042,55 @@ class _Conv3dBF16(Function):
         return dx, dw, db
 
 
+def _in16_args(x, stats):
+    """a bf16 raw conv output and the partial statistics of the conv's epilogue (the bf16 chain has no one-pass form)"""
+    _chk16(x)
+    if x.dtype != torch.bfloat16:
+        raise RuntimeError("instnorm bf16: the raw conv output must be bfloat16")
+    if stats is None:
+        raise RuntimeError("instnorm bf16: needs the conv epilogue's partial statistics")
+    _chk(stats)
+
+
+def _in16_fwd(x, stats, eps, out_bf16):
+    """THE bf16 InstanceNorm + LeakyReLU forward launch -> (y bf16 | fp32, mean, rstd)"""
+    B, V, C, mean, rstd = _in_dims(x)
+    y = torch.empty(x.shape, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=x.device)
+    nel = float(x.numel())
+    with _Guard(x, "instnorm_bf16_fwd", 8.0 * nel, nel * (4.0 if out_bf16 else 6.0)):
+        _call(_L().modet_instnorm_lrelu_fwd_stats_bf16, _p(x), _p(y), int(out_bf16), _p(mean), _p(rstd), _p(stats), stats.numel() * 4,
+              B, V, C, eps, _stream())
+    return y, mean, rstd
+
+
+def _in16_bwd(dy, x, mean, rstd):
+    """THE bf16 InstanceNorm + LeakyReLU backward launch: d_y fp32 or bf16 -> d_x bf16"""
+    B, C = x.shape[0], x.shape[-1]
+    V = x.numel() // (B * C)
+    dx = torch.empty_like(x)
+    L = _L()
+    nb = L.modet_instnorm_bf16_ws_bytes(B, V, C)
+    ws = _ws(nb, x)
+    nel = float(x.numel())
+    with _Guard(x, "instnorm_bf16_bwd", 14.0 * nel, nel * (6.0 + 2.0 * (2.0 if _isbf(dy) else 4.0))):
+        _call(L.modet_instnorm_lrelu_bwd_bf16, _p(dy), _isbf(dy), _p(x), _p(mean), _p(rstd), _p(dx), _p(ws), nb, B, V, C, _stream())
+    return dx
+
+
 class _InstNormLReLUBF16(Function):
     """InstanceNorm3d + LeakyReLU(0.1) of a bf16 raw conv output; y is bf16 (inside a chain) or fp32 (a level's output)"""
 
     @staticmethod
     def forward(ctx, x, stats, eps, out_bf16):
-        _chk16(x)
-        if x.dtype != torch.bfloat16:
-            raise RuntimeError("instnorm bf16: the raw conv output must be bfloat16")
-        if stats is None:
-            raise RuntimeError("instnorm bf16: needs the conv epilogue's partial statistics")
-        _chk(stats)
-        B, C = x.shape[0], x.shape[-1]
-        V = x.numel() // (B * C)
-        y = torch.empty(x.shape, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=x.device)
-        mean = torch.empty(B * C, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        nel = float(x.numel())
-        with _Guard(x, "instnorm_bf16_fwd", 8.0 * nel, nel * (4.0 if out_bf16 else 6.0)):
-            _lib.check(_L().modet_instnorm_lrelu_fwd_stats_bf16(_p(x), _p(y), int(out_bf16), _p(mean), _p(rstd), _p(stats),
-                                                                stats.numel() * 4, B, V, C, eps, _stream()),
-                       "modet_instnorm_lrelu_fwd_stats_bf16")
+        _in16_args(x, stats)
+        y, mean, rstd = _in16_fwd(x, stats, eps, out_bf16)
         ctx.save_for_backward(x, mean, rstd)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, mean, rstd = ctx.saved_tensors
-        dy = dy.contiguous()
-        B, C = x.shape[0], x.shape[-1]
-        V = x.numel() // (B * C)
-        dx = torch.empty_like(x)
-        L = _L()
-        nb = L.modet_instnorm_bf16_ws_bytes(B, V, C)
-        ws = _ws(nb, x)
-        nel = float(x.numel())
-        with _Guard(x, "instnorm_bf16_bwd", 14.0 * nel, nel * (6.0 + 2.0 * (2.0 if _isbf(dy) else 4.0))):
-            _lib.check(L.modet_instnorm_lrelu_bwd_bf16(_p(dy), _isbf(dy), _p(x), _p(mean), _p(rstd), _p(dx), _p(ws), nb, B, V, C,
-                                                       _stream()), "modet_instnorm_lrelu_bwd_bf16")
-        return dx, None, None, None
+        return _in16_bwd(dy.contiguous(), x, mean, rstd), None, None, None
 
 
 class _InstNormLReLUBF16PoolSplit(Function):
@@ -2144,35 +2102,23 @@ class _InstNormLReLUBF16PoolSplit(Function):
 
     @staticmethod
     def forward(ctx, x, stats, eps, Bh, features16=False):
-        _chk16(x)
-        if x.dtype != torch.bfloat16:
-            raise RuntimeError("instnorm bf16: the raw conv output must be bfloat16")
-        if stats is None:
-            raise RuntimeError("instnorm bf16: needs the conv epilogue's partial statistics")
-        _chk(stats)
+        _in16_args(x, stats)
         _rank5("instnorm bf16", "the raw conv output", x)
         B, D, H, W, C = x.shape
         if not 0 < Bh < B:
             raise RuntimeError(f"instnorm bf16: split {Bh} is not inside the batch of {tuple(x.shape)}")
-        V = D * H * W
-        L = _L()
-        y = torch.empty(x.shape, dtype=torch.bfloat16 if features16 else torch.float32, device=x.device)
-        mean = torch.empty(B * C, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        pooled = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
-        nel = float(x.numel())
         if features16:
             # one pass: bf16 features + the pooled tensor from their fp32 values (pooling the ROUNDED features costs the gradient)
+            y = torch.empty_like(x)
+            *_, mean, rstd = _in_dims(x)
+            pooled = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
+            nel = float(x.numel())
             with _Guard(x, "instnorm_bf16_fwd", 9.0 * nel, nel * 4.5):
-                _lib.check(L.modet_instnorm_lrelu_fwd_stats_pool_bf16(_p(x), _p(y), _p(pooled), _p(mean), _p(rstd), _p(stats),
-                                                                      stats.numel() * 4, B, D, H, W, C, eps, _stream()),
-                           "modet_instnorm_lrelu_fwd_stats_pool_bf16")
+                _call(_L().modet_instnorm_lrelu_fwd_stats_pool_bf16, _p(x), _p(y), _p(pooled), _p(mean), _p(rstd), _p(stats),
+                      stats.numel() * 4, B, D, H, W, C, eps, _stream())
         else:
-            with _Guard(x, "instnorm_bf16_fwd", 8.0 * nel, nel * 6.0):
-                _lib.check(L.modet_instnorm_lrelu_fwd_stats_bf16(_p(x), _p(y), 0, _p(mean), _p(rstd), _p(stats), stats.numel() * 4, B,
-                                                                 V, C, eps, _stream()), "modet_instnorm_lrelu_fwd_stats_bf16")
-            with _Guard(y, "avgpool2_fwd", y.numel(), 4.5 * y.numel()):
-                _lib.check(L.modet_avgpool2_fwd(_p(y), _p(pooled), B, D, H, W, C, _stream()), "modet_avgpool2_fwd")
+            y, mean, rstd = _in16_fwd(x, stats, eps, False)
+            pooled = _pool_fwd(y)
         ctx.save_for_backward(x, mean, rstd)
         ctx.Bh = Bh
         ctx.set_materialize_grads(False)
@@ -2196,39 +2142,34 @@ class _InstNormLReLUBF16PoolSplit(Function):
         x, mean, rstd = ctx.saved_tensors
         B, D, H, W, C = x.shape
         Bh = ctx.Bh
-        V = D * H * W
-        L = _L()
+        if gy is None:
+            return _in16_bwd(_halves(ga, gb, Bh, x.shape), x, mean, rstd), None, None, None, None
+        gy = gy.contiguous()
+        ga = None if ga is None else ga.contiguous()
+        gb = None if gb is None else gb.contiguous()
         dx = torch.empty_like(x)
-        nb = L.modet_instnorm_bf16_ws_bytes(B, V, C)
+        L = _L()
+        nb = L.modet_instnorm_bf16_ws_bytes(B, D * H * W, C)
         ws = _ws(nb, x)
         nel = float(x.numel())
-        if gy is not None:
-            gy = gy.contiguous()
-            ga = None if ga is None else ga.contiguous()
-            gb = None if gb is None else gb.contiguous()
-            with _Guard(x, "instnorm_bf16_bwd", 15.0 * nel, nel * 14.5):
-                _lib.check(L.modet_instnorm_lrelu_bwd_pool_bf16(_p(gy), _p(ga), _p(gb), Bh, _p(x), _p(mean), _p(rstd), _p(dx), _p(ws),
-                                                                nb, B, D, H, W, C, _stream()), "modet_instnorm_lrelu_bwd_pool_bf16")
-            return dx, None, None, None, None
-        dy = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        for sl, g in ((slice(0, Bh), ga), (slice(Bh, B), gb)):
-            if g is None:
-                dy[sl].zero_()
-            else:
-                dy[sl].copy_(g)
-        with _Guard(x, "instnorm_bf16_bwd", 14.0 * nel, nel * 14.0):
-            _lib.check(L.modet_instnorm_lrelu_bwd_bf16(_p(dy), 0, _p(x), _p(mean), _p(rstd), _p(dx), _p(ws), nb, B, V, C, _stream()),
-                       "modet_instnorm_lrelu_bwd_bf16")
+        with _Guard(x, "instnorm_bf16_bwd", 15.0 * nel, nel * 14.5):
+            _call(L.modet_instnorm_lrelu_bwd_pool_bf16, _p(gy), _p(ga), _p(gb), Bh, _p(x), _p(mean), _p(rstd), _p(dx), _p(ws), nb,
+                  B, D, H, W, C, _stream())
         return dx, None, None, None, None
+
+
+def _conv_ins_head_bf16(inp, w1, b1, w2, b2, eps):
+    """ConvInsBlock -> conv with bf16 storage: the nodes the two pair forms share -> (raw bf16 output of the second conv, its statistics)"""
+    raw1, st1 = _Conv3dBF16.apply(inp, w1, b1)
+    y1 = _InstNormLReLUBF16.apply(raw1, st1, eps, True)
+    return _Conv3dBF16.apply(y1, w2, b2)
 
 
 def conv_ins_pair_bf16_pool_split(inp, w1, b1, w2, b2, Bh, eps=1e-5, features16=False):
     """conv_ins_pair_bf16 whose output goes to AvgPool3d(2) and, split into its two batch halves, to the level's consumers:
     (pooled, y[:Bh], y[Bh:]); see _InstNormLReLUBF16PoolSplit.  features16: the two halves are stored as bf16 and handed out as
     fp32 handles with ``.data16`` (only level_attention_bf16 understands those)."""
-    raw1, st1 = _Conv3dBF16.apply(inp, w1, b1)
-    y1 = _InstNormLReLUBF16.apply(raw1, st1, eps, True)
-    raw2, st2 = _Conv3dBF16.apply(y1, w2, b2)
+    raw2, st2 = _conv_ins_head_bf16(inp, w1, b1, w2, b2, eps)
     return _InstNormLReLUBF16PoolSplit.apply(raw2, st2, eps, Bh, features16)
 
 
@@ -2242,7 +2183,5 @@ def feature_handle_like(new, old):
 
 def conv_ins_pair_bf16(inp, w1, b1, w2, b2, eps=1e-5):
     """ConvInsBlock -> ConvInsBlock with bf16 storage inside the chain: fp32 (or bf16) in, fp32 out"""
-    raw1, st1 = _Conv3dBF16.apply(inp, w1, b1)
-    y1 = _InstNormLReLUBF16.apply(raw1, st1, eps, True)
-    raw2, st2 = _Conv3dBF16.apply(y1, w2, b2)
+    raw2, st2 = _conv_ins_head_bf16(inp, w1, b1, w2, b2, eps)
     return _InstNormLReLUBF16.apply(raw2, st2, eps, False)
