@@ -1750,7 +1750,7 @@ inline WgPlan plan_wgrad(int B, int D, int H, int W, int Cin, int Cout) {
 // the family from them, so a buffer is sized for the kernel that runs.  (The families' interfaces: conv3d_internal.h.)
 // EXACT: the exact-f32 MFMA kernels of this file; DIRECT: its conv_direct_kernel (small volumes, plain launches only); the bf16x3
 // families: SPLIT tiled (conv3d_bf16.hip), X3 z-march (conv3d_x3.hip), WTR transpose-read weight gradient (conv3d_wtr.hip), Q channel quads (conv3d_q.hip)
-enum ConvFamily { FAM_EXACT = 0, FAM_SPLIT = 1, FAM_X3 = 2, FAM_DIRECT = 3, FAM_WTR = 4, FAM_Q = 5 };
+// (enum ConvFamily and conv_x3_on(), the MODET_CONV_X3 switch: conv3d_internal.h -- the bf16-storage routes share them)
 enum ConvVariant { CONV_PLAIN = 0, CONV_ACT = 1, CONV_NORMIN = 2, CONV_STATS = 3 };      // what a forward / data-gradient launch fuses
 
 // The A/B switches below (MODET_CONV_*) exist in tuning builds only: the product library reads no environment variable.
@@ -1764,7 +1764,6 @@ static bool use_split(int Cin, int Cout, int64_t nvox) {
   if (mode == 1) return true;
   return nvox >= 16000 && Cin >= 16 && Cin % 16 == 0 && Cout >= 16;
 }
-static bool conv_x3_on() { static const bool on = modet_tuning_env("MODET_CONV_X3") != '0'; return on; }      // one switch, both routes
 
 // A convolution AS CONVOLVED: the data gradient convolves d_y, so it passes (Cout, Cin) of its layer.
 static ConvFamily route_conv(int B, int D, int H, int W, int Cin, int Cout, int variant) {

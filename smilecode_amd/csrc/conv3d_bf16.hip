@@ -777,19 +777,21 @@ inline WgBf16Plan plan_wgrad_bf16(int B, int D, int H, int W, int Cin, int Cout)
 
 struct Bf16Plan { int tz, ty, ck, nt, nstage, cinp, coutp, ksteps; };
 inline int round_up_i(int a, int b) { return (a + b - 1) / b * b; }
-inline Bf16Plan plan_bf16(int64_t V, int Cin, int Cout) {
+// The tiled kernel's configuration.  sp = 1: bf16 storage; sp = 3: the fp32 emulation, whose tile takes three LDS planes (hi / mid /
+// lo pieces): channel chunks of at most 16, and with 16 the large-volume tile is 2 x 8 rows instead of 4 x 8.
+inline Bf16Plan plan_tiled(int64_t V, int Cin, int Cout, int sp) {
   Bf16Plan p;
   p.cinp = round_up_i(Cin, 8);
-  p.ck = p.cinp % 32 == 0 ? 32 : (p.cinp % 16 == 0 ? 16 : 8);
+  p.ck = (sp == 1 && p.cinp % 32 == 0) ? 32 : (p.cinp % 16 == 0 ? 16 : 8);
   p.nstage = p.cinp / p.ck;
   p.nt = Cout <= 16 ? 1 : 2;
   p.coutp = round_up_i(Cout, p.nt * 16);
   p.ksteps = (27 * p.ck + 31) / 32;
-  if (false && V >= 500000 && p.ck <= 16 && p.nt == 1) { p.tz = 8; p.ty = 8; }
-  else if (V >= 60000) { p.tz = 4; p.ty = 8; }
+  if (V >= 60000) { p.tz = (sp == 3 && p.ck == 16) ? 2 : 4; p.ty = 8; }
   else { p.tz = 2; p.ty = 4; }
   return p;
 }
+inline int tiled_tiles_per_sample(int D, int H, int W, const Bf16Plan& p) { return cdiv(W, TX) * cdiv(H, p.ty) * cdiv(D, p.tz); }
 
 inline size_t bf16_wpk_elems(int Cin, int Cout) {
   // generous: any plan pads Cin to a multiple of 8 and the k index to 32 per step (7 steps per 8 channels, 14 per 16,
@@ -797,107 +799,84 @@ inline size_t bf16_wpk_elems(int Cin, int Cout) {
   return (size_t)28 * round_up_i(Cin, 32) * round_up_i(Cout, 32) + 1024;
 }
 
-template <bool IN_BF16, bool OUT_BF16, bool STATS>
-int launch_bf16(modet_step_ctx* step, const void* x, const float* w, const float* bias, void* y, void* ws, float* stats, int B,
-                int D, int H, int W, int Cin, int Cout, int mode, hipStream_t s) {
-  const int64_t V = (int64_t)D * H * W;
-  const Bf16Plan p = plan_bf16(V, Cin, Cout);
-  unsigned short* wpk = (unsigned short*)ws;
-  const int total = p.nstage * p.ksteps * p.coutp * 32;
-  if (const unsigned short* pre = prepacked_bf16_or_record(step, PackBKey{w, Cin, Cout, p.coutp, p.ck, p.nstage, p.ksteps, mode, 1, 0}))
-    wpk = const_cast<unsigned short*>(pre);
-  else
-    hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(cdiv(total, 256) > 1024 ? 1024 : cdiv(total, 256)), dim3(256), 0, s, w, wpk,
-                       Cin, Cout, p.coutp, p.ck, p.nstage, p.ksteps, mode, 1);
-  const int tiles_x = cdiv(W, TX), tiles_y = cdiv(H, p.ty), tiles_z = cdiv(D, p.tz);
-  const dim3 grid(tiles_x * tiles_y * tiles_z, p.coutp / (p.nt * 16), B);
-  float* shift = nullptr;
-  float* rows = nullptr;
-  if (STATS) {
-    shift = stats;
-    rows = stats + (size_t)B * Cout;
-    hipLaunchKernelGGL(conv_shift_bf16_kernel<IN_BF16>, dim3(cdiv(B * Cout, 4)), dim3(256), 0, s, x, w, bias, shift, B, D, H, W,
-                       Cin, Cout);
-  }
-#define BF_LAUNCH(TZ_, TY_, CK_, NT_)                                                                                     \
-  hipLaunchKernelGGL((conv3d_bf16_kernel<TZ_, TY_, CK_, NT_, IN_BF16, OUT_BF16, STATS>), grid, dim3(NTHR), 0, s, x,        \
-                     (const uint4*)wpk, bias, y, rows, (const float*)shift, D, H, W, Cin, Cout, p.coutp, p.nstage, tiles_x, tiles_y, 0)
-#define BF_CK(TZ_, TY_, NT_)                                  \
-  do {                                                        \
-    if (p.ck == 8) BF_LAUNCH(TZ_, TY_, 8, NT_);               \
-    else if (p.ck == 16) BF_LAUNCH(TZ_, TY_, 16, NT_);        \
-    else BF_LAUNCH(TZ_, TY_, 32, NT_);                        \
-  } while (0)
-  if (p.tz == 8) {                       // ck <= 16, nt == 1 by construction
-    if (p.ck == 8) BF_LAUNCH(8, 8, 8, 1); else BF_LAUNCH(8, 8, 16, 1);
-  } else if (p.tz == 4) {
-    if (p.nt == 1) BF_CK(4, 8, 1); else BF_CK(4, 8, 2);
-  } else {
-    if (p.nt == 1) BF_CK(2, 4, 1); else BF_CK(2, 4, 2);
-  }
-#undef BF_CK
-#undef BF_LAUNCH
-  return modet_launch_status();
+// the shift of the fused statistics, for the tiled and the z-march forward alike: shift = the [B][Cout] head of the statistics buffer
+inline void launch_shift(bool x_bf16, const void* x, const float* w, const float* bias, float* shift, int B, int D, int H, int W,
+                         int Cin, int Cout, hipStream_t s) {
+  if (x_bf16) hipLaunchKernelGGL(conv_shift_bf16_kernel<true>, dim3(cdiv(B * Cout, 4)), dim3(256), 0, s, x, w, bias, shift, B, D, H, W, Cin, Cout);
+  else hipLaunchKernelGGL(conv_shift_bf16_kernel<false>, dim3(cdiv(B * Cout, 4)), dim3(256), 0, s, x, w, bias, shift, B, D, H, W, Cin, Cout);
 }
 
-// ---- fp32 emulation ("bf16x3", SP = 3): fp32 in, fp32 out.  Channel chunks of at most 16 (three LDS planes per tile).
-inline Bf16Plan plan_split(int64_t V, int Cin, int Cout) {
-  Bf16Plan p;
-  p.cinp = round_up_i(Cin, 8);
-  p.ck = p.cinp % 16 == 0 ? 16 : 8;
-  p.nstage = p.cinp / p.ck;
-  p.nt = Cout <= 16 ? 1 : 2;
-  p.coutp = round_up_i(Cout, p.nt * 16);
-  p.ksteps = (27 * p.ck + 31) / 32;
-  if (V >= 60000) { p.tz = p.ck == 8 ? 4 : 2; p.ty = 8; }
-  else { p.tz = 2; p.ty = 4; }
-  return p;
-}
-
-template <bool STATS>
-int launch_split(modet_step_ctx* step, const float* x, const float* w, const float* bias, float* y, void* ws, float* stats, int B,
+// THE tiled launch: weights (the step's pre-packed copy, or packed here into ws), the shift of the fused statistics, the kernel
+// that plan_tiled chose.  SP = 1: bf16 storage (x fp32 | bf16, y fp32 | bf16); SP = 3: fp32 emulation (x, y fp32).
+template <bool IN_BF16, bool OUT_BF16, bool STATS, int SP>
+int launch_tiled(modet_step_ctx* step, const void* x, const float* w, const float* bias, void* y, void* ws, float* stats, int B,
                  int D, int H, int W, int Cin, int Cout, int mode, hipStream_t s) {
-  const int64_t V = (int64_t)D * H * W;
-  const Bf16Plan p = plan_split(V, Cin, Cout);
-  unsigned short* wpk = (unsigned short*)ws;
-  const int total = p.nstage * p.ksteps * p.coutp * 32;
-  if (const unsigned short* pre = prepacked_bf16_or_record(step, PackBKey{w, Cin, Cout, p.coutp, p.ck, p.nstage, p.ksteps, mode, 3, 0}))
-    wpk = const_cast<unsigned short*>(pre);
-  else
-    hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(cdiv(total, 256) > 1024 ? 1024 : cdiv(total, 256)), dim3(256), 0, s, w, wpk,
-                       Cin, Cout, p.coutp, p.ck, p.nstage, p.ksteps, mode, 3);
-  const int tiles_x = cdiv(W, TX), tiles_y = cdiv(H, p.ty), tiles_z = cdiv(D, p.tz);
-  const dim3 grid(tiles_x * tiles_y * tiles_z, p.coutp / (p.nt * 16), B);
-  float* shift = nullptr;
+  const Bf16Plan p = plan_tiled((int64_t)D * H * W, Cin, Cout, SP);
+  const unsigned short* wpk = prepacked_bf16_or_record(step, PackBKey{w, Cin, Cout, p.coutp, p.ck, p.nstage, p.ksteps, mode, SP, 0});
+  const int total = p.nstage * p.ksteps * p.coutp * 32;    // bf16 elements of one piece
+  if (!wpk) {
+    hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(cdiv(total, 256) > 1024 ? 1024 : cdiv(total, 256)), dim3(256), 0, s, w,
+                       (unsigned short*)ws, Cin, Cout, p.coutp, p.ck, p.nstage, p.ksteps, mode, SP);
+    wpk = (const unsigned short*)ws;
+  }
+  const int wpiece = SP == 3 ? total / 8 : 0;              // uint4 units between the hi / mid / lo weight arrays
+  const int tiles_x = cdiv(W, TX), tiles_y = cdiv(H, p.ty);
+  const dim3 grid(tiled_tiles_per_sample(D, H, W, p), p.coutp / (p.nt * 16), B);
   float* rows = nullptr;
   if (STATS) {
-    shift = stats;
+    launch_shift(IN_BF16, x, w, bias, stats, B, D, H, W, Cin, Cout, s);
     rows = stats + (size_t)B * Cout;
-    hipLaunchKernelGGL(conv_shift_bf16_kernel<false>, dim3(cdiv(B * Cout, 4)), dim3(256), 0, s, (const void*)x, w, bias, shift, B, D,
-                       H, W, Cin, Cout);
   }
-  const int wpiece = total / 8;                            // uint4 units between the hi / mid / lo weight arrays
-#define SP_LAUNCH(TZ_, TY_, CK_, NT_)                                                                                     \
-  hipLaunchKernelGGL((conv3d_bf16_kernel<TZ_, TY_, CK_, NT_, false, false, STATS, 3>), grid, dim3(NTHR), 0, s, (const void*)x, \
-                     (const uint4*)wpk, bias, (void*)y, rows, (const float*)shift, D, H, W, Cin, Cout, p.coutp, p.nstage, tiles_x, \
+#define T_LAUNCH(TZ_, TY_, CK_, NT_)                                                                                       \
+  hipLaunchKernelGGL((conv3d_bf16_kernel<TZ_, TY_, CK_, NT_, IN_BF16, OUT_BF16, STATS, SP>), grid, dim3(NTHR), 0, s, x,     \
+                     (const uint4*)wpk, bias, y, rows, (const float*)stats, D, H, W, Cin, Cout, p.coutp, p.nstage, tiles_x, \
                      tiles_y, wpiece)
-  if (p.tz == 4) { if (p.nt == 1) SP_LAUNCH(4, 8, 8, 1); else SP_LAUNCH(4, 8, 8, 2); }
-  else if (p.ty == 8) { if (p.nt == 1) SP_LAUNCH(2, 8, 16, 1); else SP_LAUNCH(2, 8, 16, 2); }
-  else if (p.ck == 8) { if (p.nt == 1) SP_LAUNCH(2, 4, 8, 1); else SP_LAUNCH(2, 4, 8, 2); }
-  else { if (p.nt == 1) SP_LAUNCH(2, 4, 16, 1); else SP_LAUNCH(2, 4, 16, 2); }
-#undef SP_LAUNCH
+#define T_NT(TZ_, TY_, CK_) do { if (p.nt == 1) T_LAUNCH(TZ_, TY_, CK_, 1); else T_LAUNCH(TZ_, TY_, CK_, 2); } while (0)
+  // every (tz, ty, ck) of plan_tiled; the instantiations of one SP are the ones its plans can name
+  const int cfg = p.tz * 1000 + p.ty * 100 + p.ck;
+  if (cfg == 2408) T_NT(2, 4, 8);
+  else if (cfg == 2416) T_NT(2, 4, 16);
+  else if (cfg == 4808) T_NT(4, 8, 8);
+  else if constexpr (SP == 1) {
+    if (cfg == 2432) T_NT(2, 4, 32);
+    else if (cfg == 4816) T_NT(4, 8, 16);
+    else if (cfg == 4832) T_NT(4, 8, 32);
+    else return MODET_ERR_UNSUPPORTED;
+  } else {
+    if (cfg == 2816) T_NT(2, 8, 16);
+    else return MODET_ERR_UNSUPPORTED;
+  }
+#undef T_NT
+#undef T_LAUNCH
   return modet_launch_status();
 }
 
-inline int bf16_tiles_per_sample(int D, int H, int W, int Cin, int Cout) {
-  const Bf16Plan p = plan_bf16((int64_t)D * H * W, Cin, Cout);
-  return cdiv(W, TX) * cdiv(H, p.ty) * cdiv(D, p.tz);
+// THE tail of every 16-bit weight gradient: the two reduction stages of job j, queued in the caller's step context or launched
+// now -- with the arguments wgrad_bf16_colsum_many_kernel / wgrad_bf16_reduce_many_kernel take from the same job
+int reduce_partials(modet_step_ctx* defer, const BRedJob& j, hipStream_t s) {
+  if (defer) {
+    std::lock_guard<std::mutex> lk(defer->mu);
+    defer->brjobs.push_back(j);
+    return modet_launch_status();
+  }
+  hipLaunchKernelGGL(wgrad_bf16_colsum_kernel, dim3(colsum_blocks(j.row_fl, j.gx)), dim3(256), 0, s, j.part, j.red, j.gx, j.row_fl);
+  hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3(cdiv(j.Cout * j.Cin * 27 + j.Cout, 256)), dim3(256), 0, s, (const float*)j.red,
+                     j.dw, j.dbias, j.Cin, j.Cout, j.cib, j.u, j.ntb, 1, j.gy, j.n_coblk, j.layout);
+  return modet_launch_status();
 }
 
-// MODET_CONV_X3 = 0 keeps the tiled kernels (A/B measurements); otherwise the z-marching kernel takes the few-channel layers
-inline bool x3_on() {
-  static const bool on = modet_tuning_env("MODET_CONV_X3") != '0';
-  return on;
+// ---- Which kernel runs a bf16-storage convolution: the tiled kernels of this file (FAM_SPLIT, reported as 1) or the one-piece
+// z-march of conv3d_x3.hip (FAM_X3, reported as 2).  Written ONCE, as route_conv / route_wgrad in conv3d.hip are: the entry
+// points, the size queries and the report below switch on these two and on nothing else.
+// A convolution AS CONVOLVED: the data gradient convolves d_y (always bf16), so it passes (Cout, Cin, 1) of its layer.
+// The size queries do not know the activation's type and pass x_bf16 = 0.  It makes no difference: the entry points accept
+// a bf16 activation only with Cin % 8 == 0, and the march's one objection to bf16 input is Cin % 8 != 0 (the 16-byte loads of its
+// staging), so for every accepted call the family is the same for both types (tests/test_cpu.py holds the table to that).
+ConvFamily route_conv16(int B, int D, int H, int W, int Cin, int Cout, int x_bf16) {
+  return conv_x3_on() && modetx_x3_bf16_eligible(B, D, H, W, Cin, Cout, x_bf16) ? FAM_X3 : FAM_SPLIT;
+}
+ConvFamily route_wgrad16(int B, int D, int H, int W, int Cin, int Cout) {
+  return conv_x3_on() && modetx_x3_bf16_wgrad_eligible(B, D, H, W, Cin, Cout) ? FAM_X3 : FAM_SPLIT;
 }
 
 }  // namespace
@@ -909,46 +888,28 @@ size_t modetx_split_ws_bytes(int Cin, int Cout) {
   return 3 * bf16_wpk_elems(m, m) * sizeof(unsigned short);
 }
 size_t modetx_split_stats_bytes(int B, int D, int H, int W, int Cin, int Cout) {
-  const Bf16Plan p = plan_split((int64_t)D * H * W, Cin, Cout);
-  const size_t tiles = (size_t)cdiv(W, TX) * cdiv(H, p.ty) * cdiv(D, p.tz);
+  const size_t tiles = tiled_tiles_per_sample(D, H, W, plan_tiled((int64_t)D * H * W, Cin, Cout, 3));
   return ((size_t)B * Cout + (size_t)B * tiles * Cout * 2) * sizeof(float);
 }
 int modetx_split_conv(modet_step_ctx* step, const float* x, const float* w, const float* bias, float* y, void* ws, float* stats,
                       int B, int D, int H, int W, int Cin, int Cout, int mode, hipStream_t s) {
-  return stats ? launch_split<true>(step, x, w, bias, y, ws, stats, B, D, H, W, Cin, Cout, mode, s)
-               : launch_split<false>(step, x, w, bias, y, ws, nullptr, B, D, H, W, Cin, Cout, mode, s);
+  return stats ? launch_tiled<false, false, true, 3>(step, x, w, bias, y, ws, stats, B, D, H, W, Cin, Cout, mode, s)
+               : launch_tiled<false, false, false, 3>(step, x, w, bias, y, ws, nullptr, B, D, H, W, Cin, Cout, mode, s);
 }
 
 // ---- conv3d_x3.hip's weight-gradient kernel writes this file's partial layout (fragment-major tiles, slot = group * 3 + dx,
-// bias slot last): its two reduction stages run here, immediately or queued in the caller's step context
+// bias slot last; layout 1: its N-packed form): ntb = 1, gy = 1, n_coblk = 1
 int modetx_wgrad_partials_reduce(modet_step_ctx* defer, const float* part, float* red, float* dw, float* db, int gx, int Cin,
                                  int Cout, int cib, int u, int layout, hipStream_t s) {
-  const int red_fl = (u * (layout == 1 ? 2 : 3) + 1) * 256;     // ntb = 1, gy = 1, n_coblk = 1
-  const int64_t row_fl = red_fl;
-  if (defer) {
-    std::lock_guard<std::mutex> lk(defer->mu);
-    defer->brjobs.push_back(BRedJob{part, red, dw, db, row_fl, gx, Cin, Cout, cib, u, 1, 1, 1, layout});
-    return modet_launch_status();
-  }
-  hipLaunchKernelGGL(wgrad_bf16_colsum_kernel, dim3(colsum_blocks(row_fl, gx)), dim3(256), 0, s, part, red, gx, row_fl);
-  hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3(cdiv(Cout * Cin * 27 + Cout, 256)), dim3(256), 0, s, (const float*)red, dw, db,
-                     Cin, Cout, cib, u, 1, 1, 1, 1, layout);
-  return modet_launch_status();
+  const int64_t row_fl = (u * (layout == 1 ? 2 : 3) + 1) * 256;
+  return reduce_partials(defer, BRedJob{part, red, dw, db, row_fl, gx, Cin, Cout, cib, u, 1, 1, 1, layout}, s);
 }
 
 // ---- conv3d_wtr.hip's partial layout (layout 2): gy = (channel blocks) x (cout blocks) partial sets per workgroup row
 int modetx_wgrad_partials_reduce2(modet_step_ctx* defer, const float* part, float* red, float* dw, float* db, int gx, int gy,
                                   int Cin, int Cout, int nq, int mt, int nt, int n_coblk, hipStream_t s) {
   const int64_t row_fl = (int64_t)gy * (mt + 1) * nt * 256;
-  if (defer) {
-    std::lock_guard<std::mutex> lk(defer->mu);
-    defer->brjobs.push_back(BRedJob{part, red, dw, db, row_fl, gx, Cin, Cout, nq, mt, nt, gy, n_coblk, 2});
-    return modet_launch_status();
-  }
-  hipLaunchKernelGGL(wgrad_bf16_colsum_kernel, dim3(colsum_blocks(row_fl, gx)), dim3(256), 0, s, part, red, gx, row_fl);
-  hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3(cdiv(Cout * Cin * 27 + Cout, 256)), dim3(256), 0, s, (const float*)red, dw, db,
-                     Cin, Cout, nq, mt, nt, 1, gy, n_coblk, 2);
-  return modet_launch_status();
+  return reduce_partials(defer, BRedJob{part, red, dw, db, row_fl, gx, Cin, Cout, nq, mt, nt, gy, n_coblk, 2}, s);
 }
 
 // ---- bf16 side of modet_conv3d_wgrad_defer_flush (conv3d.hip calls it)
@@ -1012,10 +973,8 @@ void modetx_bf16_prepack_begin(modet_step_ctx* c, void* arena, hipStream_t strea
 extern "C" {
 
 int modet_conv3d_bf16_kernel_family(int B, int D, int H, int W, int Cin, int Cout, int pass, int x_bf16) {
-  if (!x3_on()) return 1;
-  if (pass == 0) return modetx_x3_bf16_eligible(B, D, H, W, Cin, Cout, x_bf16) ? 2 : 1;
-  if (pass == 1) return modetx_x3_bf16_eligible(B, D, H, W, Cout, Cin, 1) ? 2 : 1;
-  return modetx_x3_bf16_wgrad_eligible(B, D, H, W, Cin, Cout, x_bf16) ? 2 : 1;
+  if (pass == 2) return route_wgrad16(B, D, H, W, Cin, Cout);
+  return pass == 1 ? route_conv16(B, D, H, W, Cout, Cin, 1) : route_conv16(B, D, H, W, Cin, Cout, x_bf16);
 }
 
 size_t modet_conv3d_bf16_ws_bytes(int Cin, int Cout) {
@@ -1027,9 +986,8 @@ size_t modet_conv3d_bf16_stats_bytes(int B, int D, int H, int W, int Cin, int Co
   if (Cout % 4 != 0 || Cout > 128) return 0;
   // [sample][Cout] shift header, one row [Cout][2] per (sample, output tile), and a tail of 64 rows per sample for the
   // first stage of modet_instnorm_lrelu_fwd_stats_bf16's reduction
-  // the row count of the kernel with FEWER rows would do for either input type; fp32 and bf16 inputs share a plan anyway
-  const int rows = (x3_on() && modetx_x3_bf16_eligible(B, D, H, W, Cin, Cout, Cin % 8 == 0)) ? modetx_x3_bf16_rows_per_sample(B, D, H, W, Cin, Cout)
-                                                                                         : bf16_tiles_per_sample(D, H, W, Cin, Cout);
+  const int rows = route_conv16(B, D, H, W, Cin, Cout, 0) == FAM_X3 ? modetx_x3_bf16_rows_per_sample(B, D, H, W, Cin, Cout)
+                                                                   : tiled_tiles_per_sample(D, H, W, plan_tiled((int64_t)D * H * W, Cin, Cout, 1));
   return ((size_t)B * Cout + (size_t)B * (rows + 64) * Cout * 2) * sizeof(float);
 }
 
@@ -1042,19 +1000,16 @@ int modet_conv3d_bf16_fwd(const void* x, int x_bf16, const float* w, const float
   if (ws_bytes < bf16_wpk_elems(Cin, Cout) * sizeof(unsigned short)) return MODET_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   if (stats && (stats_bytes < modet_conv3d_bf16_stats_bytes(B, D, H, W, Cin, Cout) || stats_bytes == 0)) return MODET_ERR_WORKSPACE;
-  if (x3_on() && modetx_x3_bf16_eligible(B, D, H, W, Cin, Cout, x_bf16)) {
-    if (stats) {
-      if (x_bf16) hipLaunchKernelGGL(conv_shift_bf16_kernel<true>, dim3(cdiv(B * Cout, 4)), dim3(256), 0, s, x, w, bias, stats, B, D, H, W, Cin, Cout);
-      else hipLaunchKernelGGL(conv_shift_bf16_kernel<false>, dim3(cdiv(B * Cout, 4)), dim3(256), 0, s, x, w, bias, stats, B, D, H, W, Cin, Cout);
-    }
+  if (route_conv16(B, D, H, W, Cin, Cout, x_bf16) == FAM_X3) {
+    if (stats) launch_shift(x_bf16, x, w, bias, stats, B, D, H, W, Cin, Cout, s);
     return modetx_x3_bf16_conv(step, x, x_bf16, w, bias, y, 1, ws, stats, B, D, H, W, Cin, Cout, 0, s);
   }
   if (stats) {
-    return x_bf16 ? launch_bf16<true, true, true>(step, x, w, bias, y, ws, stats, B, D, H, W, Cin, Cout, 0, s)
-                  : launch_bf16<false, true, true>(step, x, w, bias, y, ws, stats, B, D, H, W, Cin, Cout, 0, s);
+    return x_bf16 ? launch_tiled<true, true, true, 1>(step, x, w, bias, y, ws, stats, B, D, H, W, Cin, Cout, 0, s)
+                  : launch_tiled<false, true, true, 1>(step, x, w, bias, y, ws, stats, B, D, H, W, Cin, Cout, 0, s);
   }
-  return x_bf16 ? launch_bf16<true, true, false>(step, x, w, bias, y, ws, nullptr, B, D, H, W, Cin, Cout, 0, s)
-                : launch_bf16<false, true, false>(step, x, w, bias, y, ws, nullptr, B, D, H, W, Cin, Cout, 0, s);
+  return x_bf16 ? launch_tiled<true, true, false, 1>(step, x, w, bias, y, ws, nullptr, B, D, H, W, Cin, Cout, 0, s)
+                : launch_tiled<false, true, false, 1>(step, x, w, bias, y, ws, nullptr, B, D, H, W, Cin, Cout, 0, s);
 }
 
 int modet_conv3d_bf16_bwd_data(const void* d_y, const float* w, void* d_x, int dx_bf16, void* ws, size_t ws_bytes, int B, int D,
@@ -1065,16 +1020,16 @@ int modet_conv3d_bf16_bwd_data(const void* d_y, const float* w, void* d_x, int d
   if (ws_bytes < bf16_wpk_elems(Cout, Cin) * sizeof(unsigned short)) return MODET_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   // a convolution of d_y (Cout channels, bf16) producing Cin channels
-  if (x3_on() && modetx_x3_bf16_eligible(B, D, H, W, Cout, Cin, 1))
+  if (route_conv16(B, D, H, W, Cout, Cin, 1) == FAM_X3)
     return modetx_x3_bf16_conv(step, d_y, 1, w, nullptr, d_x, dx_bf16, ws, nullptr, B, D, H, W, Cout, Cin, 1, s);
-  return dx_bf16 ? launch_bf16<true, true, false>(step, d_y, w, nullptr, d_x, ws, nullptr, B, D, H, W, Cout, Cin, 1, s)
-                 : launch_bf16<true, false, false>(step, d_y, w, nullptr, d_x, ws, nullptr, B, D, H, W, Cout, Cin, 1, s);
+  return dx_bf16 ? launch_tiled<true, true, false, 1>(step, d_y, w, nullptr, d_x, ws, nullptr, B, D, H, W, Cout, Cin, 1, s)
+                 : launch_tiled<true, false, false, 1>(step, d_y, w, nullptr, d_x, ws, nullptr, B, D, H, W, Cout, Cin, 1, s);
 }
 
 size_t modet_conv3d_bf16_bwd_weight_ws_bytes(int B, int D, int H, int W, int Cin, int Cout) {
   const WgBf16Plan p = plan_wgrad_bf16(B, D, H, W, Cin, Cout);
   size_t need = ((size_t)p.gx + 1) * p.gy * p.red_fl * sizeof(float);        // workgroup partials + their column sums
-  if (x3_on() && modetx_x3_bf16_wgrad_eligible(B, D, H, W, Cin, Cout, 0)) {
+  if (route_wgrad16(B, D, H, W, Cin, Cout) == FAM_X3) {      // (either kernel fits: the query sizes for the larger)
     const size_t x3 = modetx_x3_bf16_wgrad_ws_bytes(B, D, H, W, Cin, Cout);
     need = x3 > need ? x3 : need;
   }
@@ -1107,7 +1062,7 @@ static int bf16_bwd_weight_impl(const void* x, int x_bf16, const void* d_y, floa
   if (ws_bytes < modet_conv3d_bf16_bwd_weight_ws_bytes(B, D, H, W, Cin, Cout)) return MODET_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   // the few-channel full-resolution layers: z-marching kernel (conv3d_x3.hip), one bf16 piece per operand
-  if (x3_on() && modetx_x3_bf16_wgrad_eligible(B, D, H, W, Cin, Cout, x_bf16))
+  if (route_wgrad16(B, D, H, W, Cin, Cout) == FAM_X3)
     return modetx_x3_bf16_wgrad(defer, x, x_bf16, d_y, d_w, d_bias, ws, B, D, H, W, Cin, Cout, s);
   const WgBf16Plan p = plan_wgrad_bf16(B, D, H, W, Cin, Cout);
   const dim3 grid(p.gx, p.gy);
@@ -1127,18 +1082,9 @@ static int bf16_bwd_weight_impl(const void* x, int x_bf16, const void* d_y, floa
   else if (p.u == 9) WG_BF(16, 9, 1, 2, 8);
   else WG_BF(16, 3, 2, 2, 4);
 #undef WG_BF
-  const int nout = Cout * Cin * 27 + Cout;
   const int64_t row_fl = (int64_t)p.gy * p.red_fl;
   float* red = (float*)ws + (size_t)p.gx * row_fl;
-  if (defer) {
-    std::lock_guard<std::mutex> lk(defer->mu);
-    defer->brjobs.push_back(BRedJob{(const float*)ws, red, d_w, d_bias, row_fl, p.gx, Cin, Cout, p.cib, p.u, p.ntb, p.gy, p.n_coblk, 0});
-    return modet_launch_status();
-  }
-  hipLaunchKernelGGL(wgrad_bf16_colsum_kernel, dim3(colsum_blocks(row_fl, p.gx)), dim3(256), 0, s, (const float*)ws, red, p.gx, row_fl);
-  hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3(cdiv(nout, 256)), dim3(256), 0, s, (const float*)red, d_w, d_bias, Cin, Cout,
-                     p.cib, p.u, p.ntb, 1, p.gy, p.n_coblk, 0);
-  return modet_launch_status();
+  return reduce_partials(defer, BRedJob{(const float*)ws, red, d_w, d_bias, row_fl, p.gx, Cin, Cout, p.cib, p.u, p.ntb, p.gy, p.n_coblk, 0}, s);
 }
 
 }  // extern "C"

@@ -5,6 +5,13 @@
 #include "common.h"
 #include "step_ctx.h"
 
+// ---- the kernel families (the values: include/modet_hip.h, modet_conv3d_kernel_family_v / modet_conv3d_bf16_kernel_family) and
+// the ONE switch between the z-march and the other families, shared by the fp32 routes (conv3d.hip: route_conv, route_wgrad) and
+// the bf16-storage routes (conv3d_bf16.hip: route_conv16, route_wgrad16, which only know SPLIT = tiled and X3)
+enum ConvFamily { FAM_EXACT = 0, FAM_SPLIT = 1, FAM_X3 = 2, FAM_DIRECT = 3, FAM_WTR = 4, FAM_Q = 5 };
+// MODET_CONV_X3 = 0 (tuning builds only) keeps the z-march kernels out of every route (A/B measurements)
+inline bool conv_x3_on() { static const bool on = modet_tuning_env("MODET_CONV_X3") != '0'; return on; }
+
 // ---- conv3d_bf16.hip: tiled bf16x3 on fp32 tensors ("split": six exact bf16 piece products per multiply, error <= 3 * 2^-24 |a b|),
 // the reductions of the 16-bit weight-gradient partials, the 16-bit side of modet_conv3d_prepack_* / _wgrad_defer_flush
 bool modetx_split_eligible(int Cin, int Cout);
@@ -36,12 +43,13 @@ size_t modetx_x3_wgrad_ws_bytes(int B, int D, int H, int W, int Cin, int Cout);
 int modetx_x3_wgrad(modet_step_ctx* defer, const float* x, const float* dy, float* dw, float* db, void* ws, int B, int D, int H,
                     int W, int Cin, int Cout, hipStream_t s, const float* amax = nullptr, const float* in_mean = nullptr,
                     const float* in_rstd = nullptr);
-// its bf16-storage forms (called by conv3d_bf16.hip's modet_conv3d_bf16_* entry points)
+// its bf16-storage forms (launched by conv3d_bf16.hip's modet_conv3d_bf16_* entry points; the two *_eligible predicates are for
+// route_conv16 / route_wgrad16 there and nobody else)
 bool modetx_x3_bf16_eligible(int B, int D, int H, int W, int Cin, int Cout, int x_bf16);
 int modetx_x3_bf16_rows_per_sample(int B, int D, int H, int W, int Cin, int Cout);
 int modetx_x3_bf16_conv(modet_step_ctx* step, const void* x, int x_bf16, const float* w, const float* bias, void* y, int y_bf16,
                         void* ws, float* stats, int B, int D, int H, int W, int Cin, int Cout, int mode, hipStream_t s);
-bool modetx_x3_bf16_wgrad_eligible(int B, int D, int H, int W, int Cin, int Cout, int x_bf16);
+bool modetx_x3_bf16_wgrad_eligible(int B, int D, int H, int W, int Cin, int Cout);
 size_t modetx_x3_bf16_wgrad_ws_bytes(int B, int D, int H, int W, int Cin, int Cout);
 int modetx_x3_bf16_wgrad(modet_step_ctx* defer, const void* x, int x_bf16, const void* dy, float* dw, float* db, void* ws, int B,
                          int D, int H, int W, int Cin, int Cout, hipStream_t s);

@@ -1298,10 +1298,9 @@ size_t modetx_x3_wgrad_ws_bytes(int B, int D, int H, int W, int Cin, int Cout) {
 }
 int modetx_x3_wgrad(modet_step_ctx* defer, const float* x, const float* dy, float* dw, float* db, void* ws, int B, int D, int H,
                     int W, int Cin, int Cout, hipStream_t s, const float* amax, const float* in_mean, const float* in_rstd) {
-  const bool f16p = X3_F16_FWD && amax != nullptr && (int64_t)D * H * W < (1ll << 24);
-  const X3WPlan p = x3w_plan(B, D, H, W, Cin, Cout, f16p ? 2 : 3);
   // two f16 pieces when the caller knows max |d_y| (and vouches for x: an activation), else three bf16 pieces
   const bool f16 = X3_F16_FWD && amax != nullptr && (int64_t)D * H * W < (1ll << 24);
+  const X3WPlan p = x3w_plan(B, D, H, W, Cin, Cout, f16 ? 2 : 3);
   X3WArgs a{x, dy, (float*)ws, D, H, W, Cin, Cout, p.tiles_x, p.tiles_y, p.nchunk, p.zc, p.nitems, f16 ? amax : nullptr, nullptr, in_mean, in_rstd};
 #define X3W_D(NPC_, NORM_) do { \
     if (p.cib == 4) { \
@@ -1318,12 +1317,12 @@ int modetx_x3_wgrad(modet_step_ctx* defer, const float* x, const float* dy, floa
   return modetx_wgrad_partials_reduce(defer, (const float*)ws, red, dw, db, p.gx, Cin, Cout, p.cib, p.u, p.np ? 1 : 0, s);
 }
 
-// bf16 storage: x fp32 | bf16 (Cin 8), d_y bf16; same partial layout and reduction as the fp32 form
-// Cin = 8 only: with one piece a plane of the 4 x 32 column is 6-10 MFMAs per wave, and for Cin = 4 the per-plane barrier
-// and LDS round trip outweigh them (measured 4->8 at 160x192x224, B = 2: 0.327 ms against the tiled kernel's 0.261)
-bool modetx_x3_bf16_wgrad_eligible(int B, int D, int H, int W, int Cin, int Cout, int x_bf16) {
-  (void)x_bf16;
-  return modetx_x3_wgrad_eligible(B, D, H, W, Cin, Cout) && Cin == 8 && Cout == 8;      // (8->16 at level 2: 0.143 vs 0.101 ms)
+// bf16 storage: x fp32 | bf16, d_y bf16; same partial layout and reduction as the fp32 form
+// 8 -> 8 only, so the kernel is always the N-packed form of 8-channel blocks.  With one piece a plane of the 4 x 32 column is
+// 6-10 MFMAs per wave, and for Cin = 4 the per-plane barrier and LDS round trip outweigh them (measured 4->8 at 160x192x224,
+// B = 2: 0.327 ms against the tiled kernel's 0.261); 8->16 at level 2: 0.143 vs 0.101 ms.  The input's type plays no part.
+bool modetx_x3_bf16_wgrad_eligible(int B, int D, int H, int W, int Cin, int Cout) {
+  return modetx_x3_wgrad_eligible(B, D, H, W, Cin, Cout) && Cin == 8 && Cout == 8;
 }
 size_t modetx_x3_bf16_wgrad_ws_bytes(int B, int D, int H, int W, int Cin, int Cout) {
   const X3WPlan p = x3w_plan(B, D, H, W, Cin, Cout, 1);
@@ -1333,18 +1332,11 @@ int modetx_x3_bf16_wgrad(modet_step_ctx* defer, const void* x, int x_bf16, const
                          int D, int H, int W, int Cin, int Cout, hipStream_t s) {
   const X3WPlan p = x3w_plan(B, D, H, W, Cin, Cout, 1);
   X3WArgs a{x, dy, (float*)ws, D, H, W, Cin, Cout, p.tiles_x, p.tiles_y, p.nchunk, p.zc, p.nitems, nullptr, nullptr, nullptr};
-#define X3W_L(CIB_, NCO_, NP_, X16_) hipLaunchKernelGGL((conv_x3_wgrad_kernel<CIB_, NCO_, NP_, 1, X16_>), dim3(p.gx), dim3(NTHR), 0, s, a)
-  if (p.cib == 4) {
-    if (x_bf16) return MODET_ERR_UNSUPPORTED;
-    if (p.np) X3W_L(4, 8, true, false); else X3W_L(4, 16, false, false);
-  } else if (x_bf16) {
-    if (p.np) X3W_L(8, 8, true, true); else X3W_L(8, 16, false, true);
-  } else {
-    if (p.np) X3W_L(8, 8, true, false); else X3W_L(8, 16, false, false);
-  }
-#undef X3W_L
+  if (p.cib != 8 || !p.np) return MODET_ERR_UNSUPPORTED;      // (modetx_x3_bf16_wgrad_eligible: Cin = Cout = 8)
+  if (x_bf16) hipLaunchKernelGGL((conv_x3_wgrad_kernel<8, 8, true, 1, true>), dim3(p.gx), dim3(NTHR), 0, s, a);
+  else hipLaunchKernelGGL((conv_x3_wgrad_kernel<8, 8, true, 1, false>), dim3(p.gx), dim3(NTHR), 0, s, a);
   float* red = (float*)ws + (size_t)p.gx * p.red_fl;
-  return modetx_wgrad_partials_reduce(defer, (const float*)ws, red, dw, db, p.gx, Cin, Cout, p.cib, p.u, p.np ? 1 : 0, s);
+  return modetx_wgrad_partials_reduce(defer, (const float*)ws, red, dw, db, p.gx, Cin, Cout, p.cib, p.u, 1, s);
 }
 
 // the recorded 16-bit packing jobs with layout 2 / 3 belong to this file (conv3d_bf16.hip's prepack launch skips layouts >= 2)

@@ -90,6 +90,39 @@ def test_conv_routing_matches_the_recorded_table():
         assert len(bad) == 0, f"{name}: {len(bad)} entries moved, first (volume, Cin, Cout[, pass, variant]): {where}"
 
 
+def test_conv16_routing_matches_the_recorded_table():
+    """The same for the bf16-STORAGE convolutions: modet_conv3d_bf16_kernel_family for the three passes and both input
+    types, and the EXACT values of the three size queries (pure host arithmetic), against tests/golden/conv16_routing.npz
+    (recorded by tests/golden/make_conv16_routing.py before the bf16 dispatch was restructured).  And the property the size
+    queries rely on: they are not told whether the activation is bf16, and need not be -- every entry point accepts a bf16
+    activation only with Cin % 8 == 0, and there the family does not depend on the input type."""
+    import importlib.util
+    from smilecode_amd import _lib
+    spec = importlib.util.spec_from_file_location("make_conv16_routing", os.path.join(ROOT, "tests", "golden", "make_conv16_routing.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want = np.load(os.path.join(ROOT, "tests", "golden", "conv16_routing.npz"))
+    nv, nc = len(gen.VOLUMES), len(gen.CHANNELS)
+    assert want["family"].shape == (nv, nc, nc, 3, 2) and want["family"].dtype == np.int8
+    for name in ("stats_bytes", "bwd_weight_ws_bytes", "ws_bytes"):
+        assert want[name].dtype == np.int64 and (want[name] > 0).all()
+    for p in range(3):         # a table in which a pass never takes one of the two families pins nothing about it
+        assert set(np.unique(want["family"][:, :, :, p])) == {1, 2}, f"pass {p}: {np.unique(want['family'][:, :, :, p])}"
+    got = gen.table(_lib.load())
+    assert sorted(got) == sorted(want.files)
+    for name in want.files:
+        bad = np.argwhere(got[name] != want[name])
+        if name == "ws_bytes":
+            where = [(gen.CHANNELS[i[0]], gen.CHANNELS[i[1]]) for i in bad[:5]]
+        else:
+            where = [(gen.VOLUMES[i[0]], gen.CHANNELS[i[1]], gen.CHANNELS[i[2]]) + tuple(int(v) for v in i[3:]) for i in bad[:5]]
+        assert len(bad) == 0, f"{name}: {len(bad)} entries moved, first (volume, Cin, Cout[, pass, x_bf16]): {where}"
+    cin8 = [i for i, c in enumerate(gen.CHANNELS) if c % 8 == 0]
+    fam = got["family"]
+    assert len(cin8) >= 5 and np.array_equal(fam[:, cin8, :, :, 0], fam[:, cin8, :, :, 1]), \
+        "the kernel family depends on x_bf16 at a Cin % 8 == 0: the size queries can no longer ignore the input type"
+
+
 def test_product_path_has_no_cpu_fallback():
     from smilecode_amd import ops
     x = torch.zeros(1, 4, 4, 4, 8)

@@ -38,14 +38,36 @@ CASES = [(2, 20, 24, 28, 4, 8, False), (2, 20, 24, 28, 8, 8, True), (1, 17, 12, 
          (2, 40, 50, 64, 8, 16, True), (1, 50, 61, 70, 4, 8, False), (1, 48, 52, 90, 8, 8, False), (1, 41, 70, 75, 4, 16, False)]
 
 
-@pytest.mark.parametrize("B,D,H,W,Cin,Cout,inbf", CASES)
-def test_conv_bf16_fwd_dgrad_wgrad_vs_exact_on_rounded_operands(B, D, H, W, Cin, Cout, inbf):
-    from smilecode_amd import ops
+# The tiled kernel's large-volume plan (>= 60 000 voxels per sample: 4 x 8 x 16-voxel tiles), ragged in every axis; more than 16
+# channels on one side keeps a shape off the z-march.  With the small cases above (2 x 4 x 16 tiles) every
+# (TZ, TY, CK, NT) the tiled launcher selects runs: CK = 8 / 16 / 32 input channels per stage x NT = 1 / 2 output tiles.
+TILED_LARGE = [(1, 30, 41, 50, 8, 32, True), (1, 31, 45, 44, 16, 32, False), (1, 29, 43, 49, 32, 32, True),
+               (1, 33, 38, 49, 32, 16, False), (1, 26, 50, 47, 48, 16, True)]
+# ... channel pairs whose weight gradient the library refuses (Cin > 8 and Cin % 16 != 0): forward and data gradient only
+TILED_LARGE_NO_WGRAD = [(1, 30, 41, 50, 24, 16, True), (1, 27, 46, 49, 24, 16, False)]
+CASES += TILED_LARGE
+
+
+def _operands(B, D, H, W, Cin, Cout):
     g = torch.Generator().manual_seed(Cin * 131 + Cout)
     x = torch.randn(B, Cin, D, H, W, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, 3, generator=g) / np.sqrt(27 * Cin)
     b = torch.randn(Cout, generator=g)
     dy = torch.randn(B, Cout, D, H, W, generator=g)
+    return x, w, b, dy
+
+
+def _assert_tiled(B, D, H, W, Cin, Cout, inbf, passes):
+    """the dispatch of a case that is there for the tiled kernel: it must not silently test the z-march"""
+    from smilecode_amd import ops
+    assert D * H * W >= 60000
+    for p in passes:
+        assert ops._L().modet_conv3d_bf16_kernel_family(B, D, H, W, Cin, Cout, p, int(inbf)) == 1, f"pass {p} does not take the tiled kernel"
+
+
+def _check_fwd_dgrad(x, w, b, dy, inbf):
+    from smilecode_amd import ops
+    B, Cin, D, H, W = x.shape
     xin = cl(x).bfloat16() if inbf else cl(x)
     # forward: bf16 output = one rounding of the exact result
     ref = F.conv3d(r16(x), r16(w), b.double(), padding=1)
@@ -67,6 +89,16 @@ def test_conv_bf16_fwd_dgrad_wgrad_vs_exact_on_rounded_operands(B, D, H, W, Cin,
         dx16 = ncdhw(ops.conv3d_bf16_backward_data(dycl, w.cuda(), Cin, True))
         e = (dx16 - refdx).abs()
         assert float((e - (1.01 * BF_ULP * refdx.abs() + 2e-5 * refdx.abs().max())).max()) <= 0
+    return xin, dycl
+
+
+@pytest.mark.parametrize("B,D,H,W,Cin,Cout,inbf", CASES)
+def test_conv_bf16_fwd_dgrad_wgrad_vs_exact_on_rounded_operands(B, D, H, W, Cin, Cout, inbf):
+    from smilecode_amd import ops
+    if (B, D, H, W, Cin, Cout, inbf) in TILED_LARGE:
+        _assert_tiled(B, D, H, W, Cin, Cout, inbf, (0, 1, 2))
+    x, w, b, dy = _operands(B, D, H, W, Cin, Cout)
+    xin, dycl = _check_fwd_dgrad(x, w, b, dy, inbf)
     # wgrad: fp32 accumulators over all voxels, deterministic fixed-order fp64 reduction over workgroups
     refdw = torch.nn.grad.conv3d_weight(r16(x), w.shape, r16(dy), padding=1)
     refdb = r16(dy).sum((0, 2, 3, 4))
@@ -75,6 +107,14 @@ def test_conv_bf16_fwd_dgrad_wgrad_vs_exact_on_rounded_operands(B, D, H, W, Cin,
     assert float((db.double().cpu() - refdb).abs().max()) <= 3e-5 * float(refdb.abs().max()) + 1e-5
     dw2, db2 = ops.conv3d_bf16_backward_weight(xin, dycl)
     assert torch.equal(dw, dw2) and torch.equal(db, db2), "weight gradient must be run-to-run deterministic"
+
+
+@pytest.mark.parametrize("B,D,H,W,Cin,Cout,inbf", TILED_LARGE_NO_WGRAD)
+def test_conv_bf16_fwd_dgrad_tiled_large_volume_without_wgrad(B, D, H, W, Cin, Cout, inbf):
+    """the forward and data-gradient assertions of the test above, on the tiled kernel's large-volume plan with 8 input
+    channels per stage and one output tile (24 -> 16), a channel pair that has no bf16 weight gradient"""
+    _assert_tiled(B, D, H, W, Cin, Cout, inbf, (0, 1))
+    _check_fwd_dgrad(*_operands(B, D, H, W, Cin, Cout), inbf)
 
 
 def test_bf16_step_batching_is_bit_identical():

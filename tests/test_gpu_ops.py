@@ -787,6 +787,47 @@ def test_conv_q_and_transpose_read_wgrad_vs_fp64(ops, cin, cout, shape, B):
                          what="q normin + statistics")
 
 
+@pytest.mark.parametrize("cin,cout", [(32, 16), (16, 32)])
+@pytest.mark.parametrize("B,shape", [(24, (64, 64, 64)), (110, (38, 38, 38))])
+def test_conv_split_tiled_vs_fp64(ops, B, shape, cin, cout):
+    """csrc/conv3d_bf16.hip, SP = 3 (kernel family 1: the tiled bf16x3 kernel on fp32 tensors).  The policy sends it the layers
+    with >= 16 channels on both sides past 6 000 000 voxels IN TOTAL, where the channel-quad kernel bows out, so the shapes
+    reach it through the batch: 24 x 64^3 runs the plan of samples with >= 60 000 voxels (2 x 8 x 16 tiles), 110 x 38^3 the
+    small-sample plan (2 x 4 x 16); 32 -> 16 has one output tile per workgroup, 16 -> 32 two, and each one's data gradient is
+    the other's shape (16 -> 16 is no case: with <= 16 channels on both sides the z-march takes it).  The batch is ONE random sample
+    repeated: sample 0 is held against ATen-CPU fp64 (forward, fused InstanceNorm statistics, data gradient: the fp32 kernels'
+    tolerances), every other sample must equal sample 0 bit for bit (all of grid z without a 6 M-voxel reference), and a
+    second call must equal the first.  The dispatch is asserted."""
+    import torch.nn.functional as F
+    L = ops._L()
+    assert L.modet_conv3d_kernel_family_v(B, *shape, cin, cout, 0, 0) == 1, "forward does not take the tiled bf16x3 kernel"
+    assert L.modet_conv3d_kernel_family_v(B, *shape, cin, cout, 0, 3) == 1, "forward + statistics does not take the tiled bf16x3 kernel"
+    assert L.modet_conv3d_kernel_family_v(B, *shape, cin, cout, 1, 0) == 1, "data gradient does not take the tiled bf16x3 kernel"
+    gen = torch.Generator().manual_seed(cin * 613 + cout)
+    x = torch.randn((1, cin) + shape, generator=gen).double()
+    x[:, :, :, : shape[1] // 3] = 0.25                                   # a constant region
+    w = (torch.randn((cout, cin, 3, 3, 3), generator=gen) / np.sqrt(cin * 27)).double()
+    b = (0.1 * torch.randn(cout, generator=gen)).double()
+    gy = torch.randn((1, cout) + shape, generator=gen).double()
+    ref = F.conv3d(x, w, b, padding=1)
+    refn = F.leaky_relu(F.instance_norm(ref, eps=1e-5), 0.1)
+    rx = torch.nn.grad.conv3d_input(x.shape, w, gy, padding=1)
+    wd, bd = w.float().cuda(), b.float().cuda()
+    xd = cl(x.numpy()).repeat(B, 1, 1, 1, 1)                             # materialised: B copies of the one sample
+    gd = cl(gy.numpy()).repeat(B, 1, 1, 1, 1)
+
+    def check(run, want, what, **tol):
+        y = run()
+        assert_close(ncdhw(y[:1]), want.numpy(), what=what, **tol)
+        assert torch.equal(y[1:], y[:1].expand_as(y[1:])), f"{what}: a sample differs from sample 0"
+        assert torch.equal(y, run()), f"{what}: not deterministic"
+
+    with torch.no_grad():
+        check(lambda: ops.conv3d_forward(xd, wd, bd, False), ref, "split fwd")
+        check(lambda: ops.conv3d_instnorm_lrelu(xd, wd, bd), refn, "split fwd + fused InstanceNorm statistics", atol=5e-5, rtol=5e-5)
+        check(lambda: ops.conv3d_backward_data(gd, wd, cin), rx, "split dgrad", atol=5e-5)
+
+
 @pytest.mark.parametrize("Cin,Cout,xs,ws", [(8, 8, 1.0, 0.07), (8, 8, 300.0, 0.07), (8, 16, 2e-3, 0.07), (16, 16, 1.0, 3.0),
                                             (16, 16, 1.0, 1e-3), (4, 8, 3000.0, 0.2), (8, 8, 1.0, 0.07)])
 def test_conv_forward_two_f16_pieces_range_and_accuracy(Cin, Cout, xs, ws):
