@@ -153,6 +153,14 @@ LOSS_SIGNATURES = {
     "modet_mind_fwd_bwd": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, F, P]),
 }
 
+# the mutual-information losses, a third table beside the two above: mirrors include/modet_hip_mi.h one to one, same library
+MI_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "modet_hip_mi.h")
+MI_SIGNATURES = {
+    "modet_mi_ws_bytes": (SZ, [I, I, I, I, I]),
+    "modet_mi_fwd_bwd": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, F, F, F, F, P]),
+    "modet_lmi_fwd_bwd": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, F, F, F, I, F, P]),
+}
+
 _lib = None
 
 
@@ -173,7 +181,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m smilecode_amd.build` "
             "(the ModeT hot path has no CPU / eager fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(MI_SIGNATURES.items()):
         if not hasattr(lib, name) and os.environ.get("MODET_HIP_LIB"):
             continue        # an older build loaded for A/B timing may predate an entry point; the product library may not
         fn = getattr(lib, name)

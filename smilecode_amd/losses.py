@@ -1,6 +1,6 @@
 """``NCC_vxm`` and ``Grad3d`` with the reference's class names and call signatures
 (ModeT/losses.py:6-94), computed by the HIP kernels of csrc/losses.hip; ``MIND_loss`` (Baseline methods/RCN/losses.py:333-399)
-by those of csrc/mind.hip."""
+by those of csrc/mind.hip; ``MutualInformation`` and ``localMutualInformation`` (the same file, 401-556) by those of csrc/mi.hip."""
 from __future__ import annotations
 
 import torch
@@ -66,3 +66,54 @@ class MIND_loss(torch.nn.Module):
     def forward(self, y_pred, y_true):
         self._check(y_pred, y_true)
         return ops.mind_loss(y_pred.contiguous(), y_true.contiguous())
+
+
+def _mi_check(name, y_true, y_pred):
+    for arg, t in (("y_true", y_true), ("y_pred", y_pred)):
+        if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
+            raise RuntimeError(f"{name}: {arg} must be a non-empty (B,1,D,H,W) volume, got {tuple(t.shape)}")
+    if y_pred.shape != y_true.shape:
+        raise RuntimeError(f"{name}: y_true {tuple(y_true.shape)} and y_pred {tuple(y_pred.shape)} differ in shape")
+
+
+class _ParzenMI(torch.nn.Module):
+    """what the two mutual-information terms share: the bins' parameters and their checks"""
+
+    def __init__(self, sigma_ratio, minval, maxval, num_bin):
+        super().__init__()
+        if int(num_bin) != ops.MI_BINS:
+            raise RuntimeError(f"{type(self).__name__}: only num_bin = {ops.MI_BINS} exists, got {num_bin}")
+        if not (maxval > 0 and maxval > minval and sigma_ratio > 0):
+            raise RuntimeError(f"{type(self).__name__}: needs maxval > 0, maxval > minval and sigma_ratio > 0, got minval {minval}, "
+                               f"maxval {maxval}, sigma_ratio {sigma_ratio}")
+        self.sigma_ratio, self.minval, self.maxval, self.num_bins = sigma_ratio, minval, maxval, int(num_bin)
+        self.max_clip = maxval
+
+
+class MutualInformation(_ParzenMI):
+    """-mutual information over 32 Gaussian Parzen-window bins between ``minval`` and ``maxval`` (reference Baseline
+    methods/RCN/losses.py:401-457), the first choice for CT / MR or T1 / T2 pairs.  Intensities are clamped to [0, maxval] as in
+    the reference; only ``num_bin`` = 32 exists (the kernels' tile)."""
+
+    def __init__(self, sigma_ratio=1, minval=0., maxval=1., num_bin=32):
+        super().__init__(sigma_ratio, minval, maxval, num_bin)
+
+    def forward(self, y_true, y_pred):
+        _mi_check("MutualInformation", y_true, y_pred)
+        return ops.mi_loss(y_true.contiguous(), y_pred.contiguous(), self.sigma_ratio, self.minval, self.maxval, self.num_bins)
+
+
+class localMutualInformation(_ParzenMI):
+    """the same per non-overlapping patch of ``patch_size``^3 voxels of the zero-padded volumes, averaged over all patches
+    (reference Baseline methods/RCN/losses.py:459-556); patch sizes 1..16."""
+
+    def __init__(self, sigma_ratio=1, minval=0., maxval=1., num_bin=32, patch_size=5):
+        super().__init__(sigma_ratio, minval, maxval, num_bin)
+        if int(patch_size) != patch_size or not 1 <= int(patch_size) <= ops.MI_MAX_PATCH:
+            raise RuntimeError(f"localMutualInformation: patch_size must be an integer in 1..{ops.MI_MAX_PATCH}, got {patch_size}")
+        self.patch_size = int(patch_size)
+
+    def forward(self, y_true, y_pred):
+        _mi_check("localMutualInformation", y_true, y_pred)
+        return ops.lmi_loss(y_true.contiguous(), y_pred.contiguous(), self.sigma_ratio, self.minval, self.maxval, self.num_bins,
+                            self.patch_size)

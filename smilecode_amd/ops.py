@@ -1809,6 +1809,85 @@ def mind_loss(a, b):
     return _MIND.apply(a, b)
 
 
+# ------------------------------------------------------------------------------------------------ mutual information
+MI_BINS = 32                     # the MFMA tile's edge: the only bin count the kernels have (csrc/mi.hip)
+MI_MAX_PATCH = 16
+# per voxel: the histogram product and each gradient product are 32 x 32 FMA (2048 FLOP) on the fp32 MFMA; the 64 Parzen weights
+# of a pass (subtract, square, scale, exp2, normalise) about 512 more.  Traffic: each pass reads both images, a gradient is
+# written once; the partials and the two 32 x 32 matrices are noise beside that
+MI_FLOP_PER_PASS = 2048.0 + 512.0
+MI_BYTES_PER_PASS = 8.0
+
+
+def _mi_args(op, y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_size=None):
+    _chk(y_true, y_pred)
+    for t in (y_true, y_pred):
+        if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
+            raise RuntimeError(f"{op}: expects non-empty (B,1,D,H,W) volumes, got {tuple(t.shape)}")
+    _same_shape(op, "y_pred", y_pred, y_true.shape, "y_true")
+    if int(num_bin) != MI_BINS:
+        raise RuntimeError(f"{op}: only num_bin = {MI_BINS} exists, got {num_bin}")
+    if not (float(maxval) > 0.0 and float(maxval) > float(minval) and float(sigma_ratio) > 0.0):
+        raise RuntimeError(f"{op}: needs maxval > 0, maxval > minval and sigma_ratio > 0, got minval {minval}, maxval {maxval}, "
+                           f"sigma_ratio {sigma_ratio}")
+    if patch_size is not None and not (int(patch_size) == patch_size and 1 <= int(patch_size) <= MI_MAX_PATCH):
+        raise RuntimeError(f"{op}: patch_size must be an integer in 1..{MI_MAX_PATCH}, got {patch_size}")
+
+
+def _mi_launch(a, b, want_a, want_b, sigma_ratio, minval, maxval, patch_size=None, grad_scale=1.0):
+    """modet_mi_fwd_bwd / modet_lmi_fwd_bwd (patch_size given): (loss (1,), grad_scale * d loss / d a or None, the same for b)"""
+    B, _, D, H, W = a.shape
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    d_a = torch.empty_like(a) if want_a else None
+    d_b = torch.empty_like(b) if want_b else None
+    L = _L()
+    nb = L.modet_mi_ws_bytes(B, D, H, W, 0 if patch_size is None else int(patch_size))
+    if nb == 0:
+        raise RuntimeError(f"mutual information: volume {tuple(a.shape)} is out of the kernels' range")
+    ws = _ws(nb, a)
+    nv = float(a.numel())
+    ngrad = int(bool(want_a)) + int(bool(want_b))
+    with _Guard(a, "mi_fwd_bwd" if patch_size is None else "lmi_fwd_bwd", MI_FLOP_PER_PASS * (1 + ngrad) * nv,
+                (MI_BYTES_PER_PASS * (1 + min(ngrad, 1)) + 4.0 * ngrad) * nv):
+        if patch_size is None:
+            _call(L.modet_mi_fwd_bwd, _p(a), _p(b), _p(loss), _p(d_a), _p(d_b), _p(ws), nb, B, D, H, W, MI_BINS, float(minval),
+                  float(maxval), float(sigma_ratio), float(grad_scale), _stream())
+        else:
+            _call(L.modet_lmi_fwd_bwd, _p(a), _p(b), _p(loss), _p(d_a), _p(d_b), _p(ws), nb, B, D, H, W, MI_BINS, float(minval),
+                  float(maxval), float(sigma_ratio), int(patch_size), float(grad_scale), _stream())
+    return loss, d_a, d_b
+
+
+class _MI(Function):
+    """one launch yields the value and whichever of the two gradients are needed (the kernels differentiate either image or
+    both); backward multiplies the saved gradients by the upstream scalar"""
+
+    @staticmethod
+    def forward(ctx, a, b, sigma_ratio, minval, maxval, num_bin, patch_size):
+        _mi_args("lmi_loss" if patch_size is not None else "mi_loss", a, b, sigma_ratio, minval, maxval, num_bin, patch_size)
+        loss, d_a, d_b = _mi_launch(a, b, ctx.needs_input_grad[0], ctx.needs_input_grad[1], sigma_ratio, minval, maxval, patch_size)
+        ctx.save_for_backward(d_a, d_b)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        d_a, d_b = ctx.saved_tensors
+        g = g.contiguous().reshape(1)
+        return (None if d_a is None else _scale_by(d_a, g)), (None if d_b is None else _scale_by(d_b, g)), None, None, None, None, None
+
+
+def mi_loss(y_true, y_pred, sigma_ratio=1, minval=0.0, maxval=1.0, num_bin=32):
+    """-mutual information of two (B,1,D,H,W) volumes over 32 Parzen-window bins, averaged over the batch.
+    reference: Baseline methods/RCN/losses.py:401-457 (MutualInformation)"""
+    return _MI.apply(y_true, y_pred, sigma_ratio, minval, maxval, num_bin, None)
+
+
+def lmi_loss(y_true, y_pred, sigma_ratio=1, minval=0.0, maxval=1.0, num_bin=32, patch_size=5):
+    """-mutual information per non-overlapping patch of patch_size^3 voxels of the zero-padded volumes, averaged over all patches.
+    reference: Baseline methods/RCN/losses.py:459-556 (localMutualInformation)"""
+    return _MI.apply(y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_size)
+
+
 # ------------------------------------------------------------------------------------------------ non-autograd
 def ncc_value_and_grad(y_true, y_pred, win=9, grad_scale=1.0):
     """(NCC_vxm(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call -- no autograd node: the
@@ -1835,6 +1914,21 @@ def mind_value_and_grad(a, b, grad_scale=1.0):
     backward with the gradient (engine.Trainer._seeded_loss)"""
     _mind_args("MIND", a, b)
     loss, d_b = _mind_launch(a, b, True, grad_scale)
+    return loss.reshape(()), d_b
+
+
+def mi_value_and_grad(y_true, y_pred, sigma_ratio=1, minval=0.0, maxval=1.0, num_bin=32, grad_scale=1.0):
+    """(mi_loss(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call -- no autograd node: the trainer
+    seeds its backward with the gradient (engine.Trainer._seeded_loss)"""
+    _mi_args("mi_loss", y_true, y_pred, sigma_ratio, minval, maxval, num_bin)
+    loss, _, d_b = _mi_launch(y_true, y_pred, False, True, sigma_ratio, minval, maxval, None, grad_scale)
+    return loss.reshape(()), d_b
+
+
+def lmi_value_and_grad(y_true, y_pred, sigma_ratio=1, minval=0.0, maxval=1.0, num_bin=32, patch_size=5, grad_scale=1.0):
+    """(lmi_loss(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call, as mi_value_and_grad"""
+    _mi_args("lmi_loss", y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_size)
+    loss, _, d_b = _mi_launch(y_true, y_pred, False, True, sigma_ratio, minval, maxval, int(patch_size), grad_scale)
     return loss.reshape(()), d_b
 
 

@@ -19,7 +19,7 @@ import torch
 
 from . import data, utils
 from .engine import Trainer, poly_lr
-from .losses import MIND_loss
+from .losses import MIND_loss, MutualInformation, localMutualInformation
 from .models import ModeT
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
@@ -88,8 +88,9 @@ def main(argv=None):
                     help="multi-GPU: all-reduce the gradients in three buckets beside the backward (three hipGraph segments)")
     ap.add_argument("--host-loader", action="store_true",
                     help="read the .pkl pair from the host every iteration instead of caching all subjects in HBM")
-    ap.add_argument("--sim", choices=("ncc", "mind"), default="ncc",
-                    help="similarity term: NCC_vxm (mono-modal, the reference's train.py) or the MIND-SSC distance MIND_loss (multi-modal pairs)")
+    ap.add_argument("--sim", choices=("ncc", "mind", "mi", "lmi"), default="ncc",
+                    help="similarity term: NCC_vxm (mono-modal, the reference's train.py), or for multi-modal pairs the MIND-SSC distance "
+                         "MIND_loss, MutualInformation (mi) or localMutualInformation over 5^3 patches (lmi)")
     args = ap.parse_args(argv)
     same_seeds(24)
     rank, local, world = init_from_env()
@@ -120,7 +121,8 @@ def main(argv=None):
         if rank == 0:
             print(ck)
     trainer = Trainer(model, lr=args.lr, max_epoch=args.max_epoch, weights=weights,   # Adam(amsgrad) + NCC + Grad3d('l2')
-                      overlap_allreduce=args.overlap_allreduce, sim=MIND_loss() if args.sim == "mind" else None)
+                      overlap_allreduce=args.overlap_allreduce,
+                      sim={"ncc": None, "mind": MIND_loss(), "mi": MutualInformation(), "lmi": localMutualInformation()}[args.sim])
     if resume is not None and not args.no_restore_optimizer and isinstance(resume.get("optimizer"), dict) \
             and "state" in resume["optimizer"]:
         # the reference saves optimizer.state_dict() but never loads it back (train.py:80-85): a resumed run restarts
