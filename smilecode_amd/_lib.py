@@ -161,6 +161,13 @@ MI_SIGNATURES = {
     "modet_lmi_fwd_bwd": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, F, F, F, I, F, P]),
 }
 
+# the SSIM3D loss, a fourth table: mirrors include/modet_hip_ssim.h one to one, same library
+SSIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "modet_hip_ssim.h")
+SSIM_SIGNATURES = {
+    "modet_ssim_ws_bytes": (SZ, [I, I, I, I, I]),
+    "modet_ssim_fwd_bwd": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, F, P]),
+}
+
 _lib = None
 
 
@@ -181,7 +188,8 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m smilecode_amd.build` "
             "(the ModeT hot path has no CPU / eager fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(MI_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(MI_SIGNATURES.items())
+                              + list(SSIM_SIGNATURES.items())):
         if not hasattr(lib, name) and os.environ.get("MODET_HIP_LIB"):
             continue        # an older build loaded for A/B timing may predate an entry point; the product library may not
         fn = getattr(lib, name)

@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import ops
-from .losses import Grad3d, MIND_loss, MutualInformation, NCC_vxm, localMutualInformation
+from .losses import SSIM3D, Grad3d, MIND_loss, MutualInformation, NCC_vxm, localMutualInformation
 from .parallel import FlatParams, broadcast_parameters
 
 
@@ -28,8 +28,8 @@ class Trainer:
     def __init__(self, model, lr=1e-4, max_epoch=30, weights=(1.0, 1.0), betas=(0.9, 0.999), eps=1e-8, group=None,
                  overlap_allreduce=False, sim=None):
         """``sim``: the similarity term, called as ``sim(fixed, y_moved)``; None = ``NCC_vxm()`` (the reference's train.py:103),
-        ``losses.MIND_loss()``, ``losses.MutualInformation()`` or ``losses.localMutualInformation()`` for multi-modal pairs, or any
-        module (one the step does not know runs through autograd).
+        ``losses.MIND_loss()``, ``losses.MutualInformation()`` or ``losses.localMutualInformation()`` for multi-modal pairs,
+        ``losses.SSIM3D()``, or any module (one the step does not know runs through autograd).
         ``overlap_allreduce``: all-reduce the gradients in three buckets while the rest of the backward runs
         (BASELINE.json configs[4]).  The backward is cut into THREE AUTOGRAD STAGES at the bucket boundaries
         (parallel.MODET_BUCKETS: per-level heads | encoder levels 3-5 | encoder levels 1-2; cut tensors = the encoder's
@@ -76,7 +76,7 @@ class Trainer:
         3 / 5 / 7 / 9 voxels, Grad3d without ``loss_mult``) on a model that hands out its channels-last results"""
         if not (self.seed_backward and type(self.reg) is Grad3d and self.reg.loss_mult is None and hasattr(self.model, "forward_cl")):
             return False
-        if type(self.sim) in (MIND_loss, MutualInformation, localMutualInformation):     # (the kernels differentiate y_moved)
+        if type(self.sim) in (MIND_loss, MutualInformation, localMutualInformation, SSIM3D):     # (the kernels differentiate y_moved)
             return True
         return type(self.sim) is NCC_vxm and len(set(self.sim._w)) == 1 and self.sim._w[0] in (3, 5, 7, 9)
 
@@ -101,6 +101,8 @@ class Trainer:
             s = self.sim
             sim, d_y = ops.lmi_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), s.sigma_ratio, s.minval,
                                               s.maxval, s.num_bins, s.patch_size, w0)
+        elif type(self.sim) is SSIM3D:
+            sim, d_y = ops.ssim_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), self.sim.window_size, w0)
         else:
             sim, d_y = ops.ncc_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), self.sim._w[0], w0)
         reg, d_flow = ops.grad3d_value_and_grad_cl(flow_cl.detach(), self.reg.penalty, w1)

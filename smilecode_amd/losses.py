@@ -1,6 +1,7 @@
 """``NCC_vxm`` and ``Grad3d`` with the reference's class names and call signatures
 (ModeT/losses.py:6-94), computed by the HIP kernels of csrc/losses.hip; ``MIND_loss`` (Baseline methods/RCN/losses.py:333-399)
-by those of csrc/mind.hip; ``MutualInformation`` and ``localMutualInformation`` (the same file, 401-556) by those of csrc/mi.hip."""
+by those of csrc/mind.hip; ``MutualInformation`` and ``localMutualInformation`` (the same file, 401-556) by those of csrc/mi.hip;
+``SSIM3D`` and ``ssim3D`` (the same file, 103-148) by those of csrc/ssim.hip."""
 from __future__ import annotations
 
 import torch
@@ -117,3 +118,38 @@ class localMutualInformation(_ParzenMI):
         _mi_check("localMutualInformation", y_true, y_pred)
         return ops.lmi_loss(y_true.contiguous(), y_pred.contiguous(), self.sigma_ratio, self.minval, self.maxval, self.num_bins,
                             self.patch_size)
+
+
+def _ssim_check(name, img1, img2, window_size, size_average):
+    if not size_average:
+        raise RuntimeError(f"{name}: size_average=False is not built (the reference's per-axis means of a 5-D map yield a (B, W) "
+                           "tensor)")
+    if not (int(window_size) == window_size and 1 <= int(window_size) <= ops.SSIM_MAX_WINDOW and int(window_size) % 2 == 1):
+        raise RuntimeError(f"{name}: window_size must be an odd integer in 1..{ops.SSIM_MAX_WINDOW}, got {window_size}")
+    if img1 is None:
+        return
+    for arg, t in (("img1", img1), ("img2", img2)):
+        if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
+            raise RuntimeError(f"{name}: {arg} must be a non-empty (B,1,D,H,W) volume, got {tuple(t.shape)}")
+    if img1.shape != img2.shape:
+        raise RuntimeError(f"{name}: img1 {tuple(img1.shape)} and img2 {tuple(img2.shape)} differ in shape")
+
+
+class SSIM3D(torch.nn.Module):
+    """1 - mean structural similarity under a zero-padded Gaussian window (sigma 1.5) of ``window_size``^3 voxels (reference
+    Baseline methods/RCN/losses.py:103-126).  Odd windows 1..11, one channel, ``size_average=True`` only."""
+
+    def __init__(self, window_size=11, size_average=True):
+        super().__init__()
+        _ssim_check("SSIM3D", None, None, window_size, size_average)
+        self.window_size, self.size_average, self.channel = int(window_size), True, 1
+
+    def forward(self, img1, img2):
+        _ssim_check("SSIM3D", img1, img2, self.window_size, self.size_average)
+        return ops.ssim_loss(img1.contiguous(), img2.contiguous(), self.window_size)
+
+
+def ssim3D(img1, img2, window_size=11, size_average=True):
+    """the mean structural similarity itself, 1 - SSIM3D (reference Baseline methods/RCN/losses.py:140-148)"""
+    _ssim_check("ssim3D", img1, img2, window_size, size_average)
+    return 1.0 - ops.ssim_loss(img1.contiguous(), img2.contiguous(), int(window_size))

@@ -1888,6 +1888,79 @@ def lmi_loss(y_true, y_pred, sigma_ratio=1, minval=0.0, maxval=1.0, num_bin=32, 
     return _MI.apply(y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_size)
 
 
+# ------------------------------------------------------------------------------------------------ SSIM3D
+SSIM_MAX_WINDOW = 11             # odd windows 1..11 are instantiated (csrc/ssim.hip)
+SSIM_TILE_Y = 16                 # the march kernel's (y, x) tile is 16 x 32: the x pass also filters the 2 p halo rows
+
+
+def _ssim_counts(window, want_a, want_b):
+    """(FLOP, bytes) per voxel of one call, this implementation's own count.  A symmetric 1-D filter
+    output costs p pair additions, p + 1 products and p accumulations; the forward filters five fields in x (over 16 + 2 p rows
+    per 16), y and z, forms three products per halo voxel and ends in about 40 operations per voxel; a gradient filters three
+    coefficient volumes and ends in 5.  Traffic: the forward reads both images and writes 2 + (gradients) coefficient volumes,
+    each gradient reads three of them and both images and writes itself; halo re-reads are served by the caches."""
+    p = int(window) // 2
+    f = 3.0 * p + 1.0
+    rows = (SSIM_TILE_Y + 2.0 * p) / SSIM_TILE_Y
+    ngrad = int(bool(want_a)) + int(bool(want_b))
+    flop = 5.0 * f * (rows + 2.0) + 3.0 * rows + 40.0 + ngrad * (3.0 * f * (rows + 2.0) + 5.0)
+    nbytes = 8.0 + (4.0 * (2 + ngrad) if ngrad else 0.0) + 24.0 * ngrad
+    return flop, nbytes
+
+
+def _ssim_args(op, img1, img2, window_size):
+    _chk(img1, img2)
+    for t in (img1, img2):
+        if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
+            raise RuntimeError(f"{op}: expects non-empty (B,1,D,H,W) volumes, got {tuple(t.shape)}")
+    _same_shape(op, "img2", img2, img1.shape, "img1")
+    if not (int(window_size) == window_size and 1 <= int(window_size) <= SSIM_MAX_WINDOW and int(window_size) % 2 == 1):
+        raise RuntimeError(f"{op}: window_size must be an odd integer in 1..{SSIM_MAX_WINDOW}, got {window_size}")
+
+
+def _ssim_launch(a, b, want_a, want_b, window_size, grad_scale=1.0):
+    """modet_ssim_fwd_bwd: (loss (1,), grad_scale * d loss / d a or None, the same for b)"""
+    B, _, D, H, W = a.shape
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    d_a = torch.empty_like(a) if want_a else None
+    d_b = torch.empty_like(b) if want_b else None
+    L = _L()
+    nb = L.modet_ssim_ws_bytes(B, D, H, W, int(window_size))
+    if nb == 0:
+        raise RuntimeError(f"ssim_loss: volume {tuple(a.shape)} is out of the kernels' range")
+    ws = _ws(nb, a)
+    nv = float(a.numel())
+    flop, nbytes = _ssim_counts(window_size, want_a, want_b)
+    with _Guard(a, "ssim_fwd_bwd", flop * nv, nbytes * nv):
+        _call(L.modet_ssim_fwd_bwd, _p(a), _p(b), _p(loss), _p(d_a), _p(d_b), _p(ws), nb, B, D, H, W, int(window_size),
+              float(grad_scale), _stream())
+    return loss, d_a, d_b
+
+
+class _SSIM(Function):
+    """one call yields the value and whichever of the two gradients are needed; backward multiplies the saved gradients by the
+    upstream scalar"""
+
+    @staticmethod
+    def forward(ctx, a, b, window_size):
+        _ssim_args("ssim_loss", a, b, window_size)
+        loss, d_a, d_b = _ssim_launch(a, b, ctx.needs_input_grad[0], ctx.needs_input_grad[1], window_size)
+        ctx.save_for_backward(d_a, d_b)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        d_a, d_b = ctx.saved_tensors
+        g = g.contiguous().reshape(1)
+        return (None if d_a is None else _scale_by(d_a, g)), (None if d_b is None else _scale_by(d_b, g)), None
+
+
+def ssim_loss(img1, img2, window_size=11):
+    """1 - mean SSIM of two (B,1,D,H,W) volumes under a zero-padded Gaussian window (sigma 1.5) of window_size^3 voxels, applied
+    as three 1-D filters.  reference: Baseline methods/RCN/losses.py:103-126 (SSIM3D)"""
+    return _SSIM.apply(img1, img2, window_size)
+
+
 # ------------------------------------------------------------------------------------------------ non-autograd
 def ncc_value_and_grad(y_true, y_pred, win=9, grad_scale=1.0):
     """(NCC_vxm(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call -- no autograd node: the
@@ -1929,6 +2002,13 @@ def lmi_value_and_grad(y_true, y_pred, sigma_ratio=1, minval=0.0, maxval=1.0, nu
     """(lmi_loss(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call, as mi_value_and_grad"""
     _mi_args("lmi_loss", y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_size)
     loss, _, d_b = _mi_launch(y_true, y_pred, False, True, sigma_ratio, minval, maxval, int(patch_size), grad_scale)
+    return loss.reshape(()), d_b
+
+
+def ssim_value_and_grad(img1, img2, window_size=11, grad_scale=1.0):
+    """(ssim_loss(img1, img2) as a device scalar, grad_scale * d loss / d img2) from one call, as mi_value_and_grad"""
+    _ssim_args("ssim_loss", img1, img2, window_size)
+    loss, _, d_b = _ssim_launch(img1, img2, False, True, window_size, grad_scale)
     return loss.reshape(()), d_b
 
 

@@ -19,7 +19,7 @@ import torch
 
 from . import data, utils
 from .engine import Trainer, poly_lr
-from .losses import MIND_loss, MutualInformation, localMutualInformation
+from .losses import SSIM3D, MIND_loss, MutualInformation, localMutualInformation
 from .models import ModeT
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
@@ -88,9 +88,10 @@ def main(argv=None):
                     help="multi-GPU: all-reduce the gradients in three buckets beside the backward (three hipGraph segments)")
     ap.add_argument("--host-loader", action="store_true",
                     help="read the .pkl pair from the host every iteration instead of caching all subjects in HBM")
-    ap.add_argument("--sim", choices=("ncc", "mind", "mi", "lmi"), default="ncc",
+    ap.add_argument("--sim", choices=("ncc", "mind", "mi", "lmi", "ssim"), default="ncc",
                     help="similarity term: NCC_vxm (mono-modal, the reference's train.py), or for multi-modal pairs the MIND-SSC distance "
-                         "MIND_loss, MutualInformation (mi) or localMutualInformation over 5^3 patches (lmi)")
+                         "MIND_loss, MutualInformation (mi) or localMutualInformation over 5^3 patches (lmi); or 1 - SSIM under an 11^3 Gaussian "
+                         "window, SSIM3D (ssim)")
     args = ap.parse_args(argv)
     same_seeds(24)
     rank, local, world = init_from_env()
@@ -122,7 +123,8 @@ def main(argv=None):
             print(ck)
     trainer = Trainer(model, lr=args.lr, max_epoch=args.max_epoch, weights=weights,   # Adam(amsgrad) + NCC + Grad3d('l2')
                       overlap_allreduce=args.overlap_allreduce,
-                      sim={"ncc": None, "mind": MIND_loss(), "mi": MutualInformation(), "lmi": localMutualInformation()}[args.sim])
+                      sim={"ncc": None, "mind": MIND_loss(), "mi": MutualInformation(), "lmi": localMutualInformation(),
+                           "ssim": SSIM3D()}[args.sim])
     if resume is not None and not args.no_restore_optimizer and isinstance(resume.get("optimizer"), dict) \
             and "state" in resume["optimizer"]:
         # the reference saves optimizer.state_dict() but never loads it back (train.py:80-85): a resumed run restarts
