@@ -168,6 +168,13 @@ SSIM_SIGNATURES = {
     "modet_ssim_fwd_bwd": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, F, P]),
 }
 
+# the flow regularisers beside Grad3d, a fifth table: mirrors include/modet_hip_reg.h one to one, same library
+REG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "modet_hip_reg.h")
+REG_SIGNATURES = {
+    "modet_reg_ws_bytes": (SZ, [I, I, I, I, I, I]),
+    "modet_reg_fwd_bwd": (I, [P, P, P, P, SZ, I, I, I, I, I, I, I, F, P]),
+}
+
 _lib = None
 
 
@@ -189,7 +196,7 @@ def load():
             "(the ModeT hot path has no CPU / eager fallback)")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(MI_SIGNATURES.items())
-                              + list(SSIM_SIGNATURES.items())):
+                              + list(SSIM_SIGNATURES.items()) + list(REG_SIGNATURES.items())):
         if not hasattr(lib, name) and os.environ.get("MODET_HIP_LIB"):
             continue        # an older build loaded for A/B timing may predate an entry point; the product library may not
         fn = getattr(lib, name)

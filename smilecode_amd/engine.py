@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import ops
-from .losses import SSIM3D, Grad3d, MIND_loss, MutualInformation, NCC_vxm, localMutualInformation
+from .losses import SSIM3D, DisplacementRegularizer, Grad3d, Grad3DiTV, MIND_loss, MutualInformation, NCC_vxm, localMutualInformation
 from .parallel import FlatParams, broadcast_parameters
 
 
@@ -26,10 +26,13 @@ def poly_lr(epoch, max_epoch=30, init_lr=1e-4, power=0.9):
 
 class Trainer:
     def __init__(self, model, lr=1e-4, max_epoch=30, weights=(1.0, 1.0), betas=(0.9, 0.999), eps=1e-8, group=None,
-                 overlap_allreduce=False, sim=None):
+                 overlap_allreduce=False, sim=None, reg=None):
         """``sim``: the similarity term, called as ``sim(fixed, y_moved)``; None = ``NCC_vxm()`` (the reference's train.py:103),
         ``losses.MIND_loss()``, ``losses.MutualInformation()`` or ``losses.localMutualInformation()`` for multi-modal pairs,
         ``losses.SSIM3D()``, or any module (one the step does not know runs through autograd).
+        ``reg``: the flow regulariser, called as ``reg(flow, fixed)``; None = ``Grad3d(penalty="l2")`` (the reference's
+        train.py:104), ``losses.Grad3DiTV()``, ``losses.DisplacementRegularizer('bending' | 'gradient-l2' | 'gradient-l1')``, or
+        any module, as for ``sim``.
         ``overlap_allreduce``: all-reduce the gradients in three buckets while the rest of the backward runs
         (BASELINE.json configs[4]).  The backward is cut into THREE AUTOGRAD STAGES at the bucket boundaries
         (parallel.MODET_BUCKETS: per-level heads | encoder levels 3-5 | encoder levels 1-2; cut tensors = the encoder's
@@ -55,7 +58,7 @@ class Trainer:
         self.seed_backward = SEED_BACKWARD  # False: the step goes through loss(...)[0].backward() (tests compare the two)
         self.lr_last = lr
         self.sim = NCC_vxm() if sim is None else sim
-        self.reg = Grad3d(penalty="l2")
+        self.reg = Grad3d(penalty="l2") if reg is None else reg
         self.buckets = None
         if overlap_allreduce:
             from .parallel import MODET_BUCKETS, BucketedAllReduce
@@ -73,8 +76,12 @@ class Trainer:
 
     def _seedable(self):
         """the step's own loss path applies: the reference's two loss terms as the HIP kernels have them (cubic NCC window of
-        3 / 5 / 7 / 9 voxels, Grad3d without ``loss_mult``) on a model that hands out its channels-last results"""
-        if not (self.seed_backward and type(self.reg) is Grad3d and self.reg.loss_mult is None and hasattr(self.model, "forward_cl")):
+        3 / 5 / 7 / 9 voxels or one of the other similarity kernels; Grad3d without ``loss_mult``, Grad3DiTV or
+        DisplacementRegularizer -- exact types, a subclass keeps the autograd expression) on a model that hands out its
+        channels-last results"""
+        if not (self.seed_backward and hasattr(self.model, "forward_cl")):
+            return False
+        if not ((type(self.reg) is Grad3d and self.reg.loss_mult is None) or type(self.reg) in (Grad3DiTV, DisplacementRegularizer)):
             return False
         if type(self.sim) in (MIND_loss, MutualInformation, localMutualInformation, SSIM3D):     # (the kernels differentiate y_moved)
             return True
@@ -105,7 +112,11 @@ class Trainer:
             sim, d_y = ops.ssim_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), self.sim.window_size, w0)
         else:
             sim, d_y = ops.ncc_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), self.sim._w[0], w0)
-        reg, d_flow = ops.grad3d_value_and_grad_cl(flow_cl.detach(), self.reg.penalty, w1)
+        if type(self.reg) is Grad3d:
+            reg, d_flow = ops.grad3d_value_and_grad_cl(flow_cl.detach(), self.reg.penalty, w1)
+        else:
+            kind = "itv" if type(self.reg) is Grad3DiTV else self.reg.energy_type
+            reg, d_flow = ops.reg_value_and_grad_cl(flow_cl.detach(), kind, w1)
         if w0 != 1.0:
             sim = sim * w0
         if w1 != 1.0:

@@ -1,7 +1,8 @@
 """``NCC_vxm`` and ``Grad3d`` with the reference's class names and call signatures
 (ModeT/losses.py:6-94), computed by the HIP kernels of csrc/losses.hip; ``MIND_loss`` (Baseline methods/RCN/losses.py:333-399)
 by those of csrc/mind.hip; ``MutualInformation`` and ``localMutualInformation`` (the same file, 401-556) by those of csrc/mi.hip;
-``SSIM3D`` and ``ssim3D`` (the same file, 103-148) by those of csrc/ssim.hip."""
+``SSIM3D`` and ``ssim3D`` (the same file, 103-148) by those of csrc/ssim.hip; ``Grad3DiTV`` and ``DisplacementRegularizer``
+(the same file, 203-268) by those of csrc/reg.hip."""
 from __future__ import annotations
 
 import torch
@@ -153,3 +154,38 @@ def ssim3D(img1, img2, window_size=11, size_average=True):
     """the mean structural similarity itself, 1 - SSIM3D (reference Baseline methods/RCN/losses.py:140-148)"""
     _ssim_check("ssim3D", img1, img2, window_size, size_average)
     return 1.0 - ops.ssim_loss(img1.contiguous(), img2.contiguous(), int(window_size))
+
+
+def _flow_check(name, flow, kind):
+    if not torch.is_tensor(flow) or flow.dim() != 5 or (kind != "itv" and flow.shape[1] != 3):
+        want = "(B,C,D,H,W)" if kind == "itv" else "(B,3,D,H,W)"
+        raise RuntimeError(f"{name}: expects a planar {want} flow, got {tuple(flow.shape) if torch.is_tensor(flow) else type(flow)}")
+    if flow.shape[0] < 1 or flow.shape[1] < 1 or min(flow.shape[2:]) < ops.REG_MIN_SIZE[kind]:
+        raise RuntimeError(f"{name}: '{kind}' needs D, H, W >= {ops.REG_MIN_SIZE[kind]} (the reference's mean of no points is NaN), "
+                           f"got {tuple(flow.shape)}")
+
+
+class Grad3DiTV(torch.nn.Module):
+    """isotropic total variation of a flow (reference Baseline methods/RCN/losses.py:203-221): the mean over the points with
+    z, y, x >= 1 of sqrt(|backward differences|^2 + 1e-6), divided by 3.  Any channel count; ``y_true`` is unused."""
+
+    def forward(self, y_pred, y_true=None):
+        _flow_check("Grad3DiTV", y_pred, "itv")
+        return ops.reg_loss(y_pred.contiguous(), "itv")
+
+
+class DisplacementRegularizer(torch.nn.Module):
+    """'bending', 'gradient-l2' or 'gradient-l1' energy of a 3-channel displacement field from central differences on its
+    interior (reference Baseline methods/RCN/losses.py:223-268).  An unknown ``energy_type`` is refused here, not at the first
+    call, and so is a field that does not have exactly 3 channels (the reference reads channels 0..2 of a wider one)."""
+
+    def __init__(self, energy_type):
+        super().__init__()
+        if energy_type not in ("bending", "gradient-l2", "gradient-l1"):
+            raise RuntimeError(f"DisplacementRegularizer: unknown energy_type {energy_type!r} (the reference knows 'bending', "
+                               "'gradient-l2' and 'gradient-l1', losses.py:259-267)")
+        self.energy_type = energy_type
+
+    def forward(self, disp, _=None):
+        _flow_check("DisplacementRegularizer", disp, self.energy_type)
+        return ops.reg_loss(disp.contiguous(), self.energy_type)

@@ -1961,6 +1961,77 @@ def ssim_loss(img1, img2, window_size=11):
     return _SSIM.apply(img1, img2, window_size)
 
 
+# ------------------------------------------------------------------------------------------------ flow regularisers beside Grad3d
+REG_KINDS = {"itv": 0, "gradient-l2": 1, "gradient-l1": 2, "bending": 3}      # the enum of include/modet_hip_reg.h
+REG_MIN_SIZE = {"itv": 2, "gradient-l2": 3, "gradient-l1": 3, "bending": 5}   # the shortest axis that holds a stencil point
+# (FLOP, bytes) per ELEMENT of the flow of one call, this implementation's own count (csrc/reg.hip): the
+# traffic is the flow read once and the gradient written once, neighbour reads are served by the caches; the arithmetic is the
+# gathered adjoint -- iTV: four norms (3 differences, 3 products, a root, a division each); gradient: 6 differences and their
+# penalties; bending: 9 axial and 12 mixed second differences of 3 operations, their squares and signed sums.
+_REG_COUNTS = {"itv": (60.0, 8.0), "gradient-l2": (20.0, 8.0), "gradient-l1": (24.0, 8.0), "bending": (110.0, 8.0)}
+
+
+def _reg_args(op, flow, kind, channels_last):
+    """(B, C, D, H, W) of a planar (B,C,D,H,W) or channels-last (B,D,H,W,3) flow that the kind accepts"""
+    if kind not in REG_KINDS:
+        raise RuntimeError(f"{op}: unknown kind {kind!r} (there are {', '.join(REG_KINDS)})")
+    _chk(flow)
+    if flow.dim() != 5:
+        raise RuntimeError(f"{op}: expects a {'channels-last (B,D,H,W,3)' if channels_last else 'planar (B,C,D,H,W)'} flow, got "
+                           f"{tuple(flow.shape)}")
+    if channels_last:
+        B, D, H, W, C = flow.shape
+        if C != 3:
+            raise RuntimeError(f"{op}: expects a channels-last (B,D,H,W,3) flow, got {tuple(flow.shape)} (a planar one goes through "
+                               "reg_loss)")
+    else:
+        B, C, D, H, W = flow.shape
+        if C != 3 and kind != "itv":
+            raise RuntimeError(f"{op}: '{kind}' takes a flow of 3 channels (B,3,D,H,W), got {tuple(flow.shape)}")
+    if B < 1 or C < 1 or min(D, H, W) < REG_MIN_SIZE[kind]:
+        raise RuntimeError(f"{op}: '{kind}' needs a non-empty flow with D, H, W >= {REG_MIN_SIZE[kind]}, got {tuple(flow.shape)}")
+    return B, C, D, H, W
+
+
+def _reg_launch(flow, kind, dims, channels_last, want_grad, grad_scale=1.0):
+    """modet_reg_fwd_bwd: (loss (1,), grad_scale * d loss / d flow in the flow's layout or None)"""
+    B, C, D, H, W = dims
+    loss = torch.empty(1, dtype=torch.float32, device=flow.device)
+    df = torch.empty_like(flow) if want_grad else None
+    L = _L()
+    nb = L.modet_reg_ws_bytes(REG_KINDS[kind], B, C, D, H, W)
+    if nb == 0:
+        raise RuntimeError(f"reg_loss: flow {tuple(flow.shape)} is out of the kernels' range")
+    ws = _ws(nb, flow)
+    flop, nbytes = _REG_COUNTS[kind]
+    with _Guard(flow, f"reg_fwd_bwd[{kind}]", flop * flow.numel(), (nbytes if want_grad else 4.0) * flow.numel()):
+        _call(L.modet_reg_fwd_bwd, _p(flow), _p(loss), _p(df), _p(ws), nb, REG_KINDS[kind], B, C, D, H, W, int(bool(channels_last)),
+              float(grad_scale), _stream())
+    return loss, df
+
+
+class _Reg(Function):
+    """like _Grad3d: the call writes value and gradient, backward multiplies the saved gradient by the upstream scalar"""
+
+    @staticmethod
+    def forward(ctx, flow, kind):
+        dims = _reg_args("reg_loss", flow, kind, False)
+        loss, df = _reg_launch(flow, kind, dims, False, ctx.needs_input_grad[0])
+        ctx.save_for_backward(df)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (df,) = ctx.saved_tensors
+        return (None if df is None else _scale_by(df, g.contiguous().reshape(1))), None
+
+
+def reg_loss(flow, kind):
+    """a regulariser of a planar flow: 'itv' (B,C,D,H,W), the isotropic total variation (reference Baseline methods/RCN/losses.py:
+    203-221), or on (B,3,D,H,W) 'gradient-l2', 'gradient-l1' and 'bending' (the same file, 223-268)"""
+    return _Reg.apply(flow, kind)
+
+
 # ------------------------------------------------------------------------------------------------ non-autograd
 def ncc_value_and_grad(y_true, y_pred, win=9, grad_scale=1.0):
     """(NCC_vxm(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call -- no autograd node: the
@@ -2029,6 +2100,14 @@ def grad3d_value_and_grad_cl(flow_cl, penalty="l2", grad_scale=1.0):
     with _Guard(flow_cl, "grad3d_fwd_bwd", 20.0 * flow_cl.numel(), 8.0 * flow_cl.numel()):
         _call(L.modet_grad3d_fwd_bwd_cl, _p(flow_cl), _p(loss), _p(df), _p(ws), nb, B, D, H, W, 1 if penalty == "l1" else 2,
               float(grad_scale), _stream())
+    return loss.reshape(()), df
+
+
+def reg_value_and_grad_cl(flow_cl, kind, grad_scale=1.0):
+    """(reg_loss(kind) as a device scalar, grad_scale * d loss / d flow) of a CHANNELS-LAST flow (B,D,H,W,3), gradient in the same
+    layout -- no autograd node, no planar copy of the flow: the counterpart of grad3d_value_and_grad_cl"""
+    dims = _reg_args("reg_loss", flow_cl, kind, True)
+    loss, df = _reg_launch(flow_cl, kind, dims, True, True, grad_scale)
     return loss.reshape(()), df
 
 

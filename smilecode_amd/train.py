@@ -19,7 +19,7 @@ import torch
 
 from . import data, utils
 from .engine import Trainer, poly_lr
-from .losses import SSIM3D, MIND_loss, MutualInformation, localMutualInformation
+from .losses import SSIM3D, DisplacementRegularizer, Grad3DiTV, MIND_loss, MutualInformation, localMutualInformation
 from .models import ModeT
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
@@ -69,7 +69,7 @@ def latest_checkpoint(model_dir):
     return os.path.join(model_dir, files[-1])
 
 
-def main(argv=None):
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--train-dir", default="/LPBA_path/Train/")
     ap.add_argument("--val-dir", default="/LPBA_path/Val/")
@@ -92,16 +92,32 @@ def main(argv=None):
                     help="similarity term: NCC_vxm (mono-modal, the reference's train.py), or for multi-modal pairs the MIND-SSC distance "
                          "MIND_loss, MutualInformation (mi) or localMutualInformation over 5^3 patches (lmi); or 1 - SSIM under an 11^3 Gaussian "
                          "window, SSIM3D (ssim)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--reg", choices=("grad3d", "itv", "gradient-l2", "gradient-l1", "bending"), default="grad3d",
+                    help="flow regulariser: Grad3d('l2') (the reference's train.py), the isotropic total variation Grad3DiTV (itv), or "
+                         "DisplacementRegularizer's central-difference gradient norms (gradient-l2, gradient-l1) or bending energy "
+                         "(bending), the usual partner of mi and mind")
+    ap.add_argument("--reg-weight", type=float, default=1, help="weight of the regulariser in the loss (the reference's weights[1])")
+    return ap
+
+
+def save_dir_name(args, num_heads, head_dim, weights):
+    """the experiment directory: the reference's name (train.py:66-68) with the similarity term in it; a regulariser other than
+    the default Grad3d with weight 1 is named too, the default leaves the name as it always was"""
+    reg = "" if (args.reg == "grad3d" and weights[1] == 1) else "{}_".format(args.reg)
+    return "modet-heads({}{}{}{}{})-rpe_headim_{}_{}_{}_reg_{}{}_lr_{}_54r/".format(*num_heads, head_dim, args.sim, weights[0], reg,
+                                                                                   weights[1], args.lr)
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
     same_seeds(24)
     rank, local, world = init_from_env()
     torch.cuda.set_device(local)
 
-    weights = [1, 1]
+    weights = [1, 1 if args.reg_weight == 1 else args.reg_weight]
     head_dim, num_heads = 6, [8, 4, 2, 1, 1]
     img_size = tuple(int(s) for s in args.img_size.split(","))
-    save_dir = "modet-heads({}{}{}{}{})-rpe_headim_{}_{}_{}_reg_{}_lr_{}_54r/".format(*num_heads, head_dim, args.sim, weights[0],
-                                                                                      weights[1], args.lr)
+    save_dir = save_dir_name(args, num_heads, head_dim, weights)
     exp_dir, log_dir = os.path.join(args.out, "experiments/" + save_dir), os.path.join(args.out, "logs/" + save_dir)
     f = None
     if rank == 0:
@@ -124,7 +140,9 @@ def main(argv=None):
     trainer = Trainer(model, lr=args.lr, max_epoch=args.max_epoch, weights=weights,   # Adam(amsgrad) + NCC + Grad3d('l2')
                       overlap_allreduce=args.overlap_allreduce,
                       sim={"ncc": None, "mind": MIND_loss(), "mi": MutualInformation(), "lmi": localMutualInformation(),
-                           "ssim": SSIM3D()}[args.sim])
+                           "ssim": SSIM3D()}[args.sim],
+                      reg={"grad3d": None, "itv": Grad3DiTV(), "gradient-l2": DisplacementRegularizer("gradient-l2"),
+                           "gradient-l1": DisplacementRegularizer("gradient-l1"), "bending": DisplacementRegularizer("bending")}[args.reg])
     if resume is not None and not args.no_restore_optimizer and isinstance(resume.get("optimizer"), dict) \
             and "state" in resume["optimizer"]:
         # the reference saves optimizer.state_dict() but never loads it back (train.py:80-85): a resumed run restarts
