@@ -515,14 +515,15 @@ size_t modet_ncc_box_ws_bytes(int B, int D, int H, int W, int wz, int wy, int wx
 int modet_ncc_fwd_bwd_box(const float* I, const float* J, float* loss, float* d_J, void* ws, size_t ws_bytes, int B, int D,
                           int H, int W, int wz, int wy, int wx, modet_stream_t stream);
 /* Grad3d (losses.py:6-31) on a planar flow (B,3,D,H,W): loss[0], d_flow (NULL to skip).
- * penalty = 1 ('l1', |forward differences|, the class default) or 2 ('l2', squared; what train.py:104 uses). */
+ * penalty = 1 ('l1', |forward differences|, the class default) or 2 ('l2', squared; what train.py:104 uses).
+ * The workspace holds one fp64 loss partial per workgroup: 8-byte aligned, else MODET_ERR_WORKSPACE. */
 size_t modet_grad3d_ws_bytes(int B, int D, int H, int W);
 int modet_grad3d_fwd_bwd(const float* flow, float* loss, float* d_flow, void* ws, size_t ws_bytes,
                          int B, int D, int H, int W, int penalty, modet_stream_t stream);
 /* Grad3d on a CHANNELS-LAST flow (B,D,H,W,3) -- the layout ModeT's last composition writes -- with
  * d_flow_cl = grad_scale * d loss / d flow in the same layout (loss[0] unscaled).  Element for element the arithmetic of
- * modet_grad3d_fwd_bwd (d_flow equal bit for bit after the layout change when grad_scale = 1; the loss is the same sum in
- * another order).  A training step uses it to skip the planar copy of the flow (losses.py:6-31 indexes (B,3,D,H,W)) and
+ * modet_grad3d_fwd_bwd (d_flow equal bit for bit after the layout change when grad_scale = 1; the loss is the same fp32
+ * terms summed in fp64 in another order, so its fp32 value has the same bits too).  A training step uses it to skip the planar copy of the flow (losses.py:6-31 indexes (B,3,D,H,W)) and
  * the copy of its gradient back. */
 int modet_grad3d_fwd_bwd_cl(const float* flow_cl, float* loss, float* d_flow_cl, void* ws, size_t ws_bytes,
                             int B, int D, int H, int W, int penalty, float grad_scale, modet_stream_t stream);

@@ -296,8 +296,9 @@ inline MarchPlan march_plan(int B, int D, int H, int W, int win) {
 }
 
 
-// loss[0] = scale * sum(part[0..n))  (fp64, fixed order); optionally adds into loss (accumulate != 0)
-__global__ void scalar_finalize_kernel(const float* __restrict__ part, int n, double scale, float* __restrict__ loss) {
+// loss[0] = scale * sum(part[0..n))  (fp64, fixed order); part in fp32 (NCC) or fp64 (Grad3d)
+template <typename T>
+__global__ void scalar_finalize_kernel(const T* __restrict__ part, int n, double scale, float* __restrict__ loss) {
   __shared__ double sm[BLK];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += BLK) s += (double)part[i];
@@ -345,9 +346,13 @@ __global__ __launch_bounds__(BLK) void ncc_cc_kernel(const float* __restrict__ s
   __shared__ float red[16];
   float lsum = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < M; i += (int64_t)gridDim.x * BLK) {
+    // symmetric in (I, J) (the two mixed products are added to each other first) and free of fma contraction (fma(a, b, c * d)
+    // rounds c * d and not a * b): with a window of one voxel the variances and the covariance cancel to the exact zeros the
+    // reference returns, and the value does not depend on which volume is called I
+#pragma clang fp contract(off)
     const float I_sum = s5[i], J_sum = s5[M + i], I2_sum = s5[2 * M + i], J2_sum = s5[3 * M + i], IJ_sum = s5[4 * M + i];
     const float u_I = I_sum / win_size, u_J = J_sum / win_size;
-    const float cross = IJ_sum - u_J * I_sum - u_I * J_sum + u_I * u_J * win_size;
+    const float cross = (IJ_sum - (u_J * I_sum + u_I * J_sum)) + (u_I * u_J) * win_size;
     const float I_var = I2_sum - 2.f * u_I * I_sum + u_I * u_I * win_size;
     const float J_var = J2_sum - 2.f * u_J * J_sum + u_J * u_J * win_size;
     const float den = I_var * J_var + 1e-5f;
@@ -386,13 +391,17 @@ constexpr int NCC_BOX_PARTS = 1024;
 // gradient back).  'l2': loss = (mean dH^2 + mean dD^2 + mean dW^2)/3; 'l1' (L1 = true): the same with |d| instead of d^2
 // (losses.py:11-27); the gradient of |t| at t = 0 is 0, as torch.abs's backward (sign(0) = 0).  df = gscale * d loss / d f
 // (gscale = the loss term's weight, train.py:127-129; the product with 1.0f is exact).
+// The loss: every element contributes ONE fp32 value (its three forward terms, the same bits in either layout) and those are
+// summed in fp64 (per thread, per workgroup, then scalar_finalize_kernel), as csrc/reg.hip does -- which elements a thread or a
+// workgroup holds depends on the layout, and fp32 partial sums made the planar and the channels-last value differ in the last
+// bit on small flows.
 template <bool L1, int CS>
 __global__ __launch_bounds__(BLK) void grad3d_kernel(const float* __restrict__ f, float* __restrict__ df,
-                                                     float* __restrict__ part, Dims d, int64_t N, float inD, float inH,
+                                                     double* __restrict__ part, Dims d, int64_t N, float inD, float inH,
                                                      float inW, float gscale) {
-  __shared__ float red[BLK / 64];
+  __shared__ double red[BLK / 64];
   const int64_t sD = (int64_t)d.H * d.W * CS, sH = (int64_t)d.W * CS;
-  float lsum = 0.f;
+  double lsum = 0.0;
   const bool small = N < (1ll << 31);
   for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < N; i += (int64_t)gridDim.x * BLK) {
     int z, y, x;
@@ -408,16 +417,24 @@ __global__ __launch_bounds__(BLK) void grad3d_kernel(const float* __restrict__ f
     const float zp = f[z + 1 < d.D ? i + sD : i], zm = f[z > 0 ? i - sD : i];
     const float yp = f[y + 1 < d.H ? i + sH : i], ym = f[y > 0 ? i - sH : i];
     const float xp = f[x + 1 < d.W ? i + CS : i], xm = f[x > 0 ? i - CS : i];
-    { const float t = zp - v; lsum = fmaf(pen(t), inD, lsum); g -= dpen(t) * inD; }
+    float e;
+    { const float t = zp - v; e = pen(t) * inD; g -= dpen(t) * inD; }
     { const float t = v - zm; g += dpen(t) * inD; }
-    { const float t = yp - v; lsum = fmaf(pen(t), inH, lsum); g -= dpen(t) * inH; }
+    { const float t = yp - v; e = fmaf(pen(t), inH, e); g -= dpen(t) * inH; }
     { const float t = v - ym; g += dpen(t) * inH; }
-    { const float t = xp - v; lsum = fmaf(pen(t), inW, lsum); g -= dpen(t) * inW; }
+    { const float t = xp - v; e = fmaf(pen(t), inW, e); g -= dpen(t) * inW; }
     { const float t = v - xm; g += dpen(t) * inW; }
+    lsum += (double)e;
     if (df) df[i] = (g * (L1 ? 1.f / 3.f : 2.f / 3.f)) * gscale;
   }
-  const float r = block_sum(lsum, red);
-  if (threadIdx.x == 0) part[blockIdx.x] = r;
+  lsum = wave_sum_d(lsum);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r = 0.0;
+    for (int k = 0; k < BLK / 64; ++k) r += red[k];
+    part[blockIdx.x] = r;
+  }
 }
 
 inline int red_grid(int64_t N) {
@@ -453,7 +470,7 @@ int modet_ncc_fwd_bwd_win_scaled(const float* I, const float* J, float* loss, fl
   do {                                                                                                                     \
     hipLaunchKernelGGL((ncc_march_kernel<W_, true>), dim3(p.grid), dim3(BLK), 0, s, I, J, (const float*)nullptr,          \
                        (const float*)nullptr, d_J ? coef : (float*)nullptr, part, d, N, p.tiles_x, p.tiles_y, p.nchunk, p.zc, 0.f); \
-    hipLaunchKernelGGL(scalar_finalize_kernel, dim3(1), dim3(BLK), 0, s, (const float*)part, p.grid, -1.0 / (double)N, loss); \
+    hipLaunchKernelGGL(scalar_finalize_kernel<float>, dim3(1), dim3(BLK), 0, s, (const float*)part, p.grid, -1.0 / (double)N, loss); \
     if (d_J)                                                                                                               \
       hipLaunchKernelGGL((ncc_march_kernel<W_, false>), dim3(p.grid), dim3(BLK), 0, s, (const float*)coef,                \
                          (const float*)nullptr, I, J, d_J, (float*)nullptr, d, N, p.tiles_x, p.tiles_y, p.nchunk, p.zc,    \
@@ -508,7 +525,7 @@ int modet_ncc_fwd_bwd_box(const float* I, const float* J, float* loss, float* d_
   const float win_size = (float)wz * (float)wy * (float)wx;
   const int gp = flat_grid(M, BLK) < NCC_BOX_PARTS ? flat_grid(M, BLK) : NCC_BOX_PARTS;
   hipLaunchKernelGGL(ncc_cc_kernel, dim3(gp), dim3(BLK), 0, s, (const float*)Y, d_J ? X : (float*)nullptr, part, M, win_size);
-  hipLaunchKernelGGL(scalar_finalize_kernel, dim3(1), dim3(BLK), 0, s, (const float*)part, gp, -1.0 / (double)M, loss);
+  hipLaunchKernelGGL(scalar_finalize_kernel<float>, dim3(1), dim3(BLK), 0, s, (const float*)part, gp, -1.0 / (double)M, loss);
   if (d_J) {
     box(X, Y, 3, B, g.Do, D, g.Ho * g.Wo, wz, g.p - wz + 1);                // adjoint z: (B, Do, Ho, Wo) -> (B, D, Ho, Wo)
     box(Y, X, 3, B * D, g.Ho, H, g.Wo, wy, g.p - wy + 1);                   // adjoint y
@@ -518,14 +535,14 @@ int modet_ncc_fwd_bwd_box(const float* I, const float* J, float* loss, float* d_
   return modet_launch_status();
 }
 
-size_t modet_grad3d_ws_bytes(int, int, int, int) { return 2048 * sizeof(float); }
+size_t modet_grad3d_ws_bytes(int, int, int, int) { return 2048 * sizeof(double); }      // one fp64 loss partial per workgroup
 
 static int grad3d_launch(const float* flow, float* loss, float* d_flow, void* ws, size_t ws_bytes, int B, int D, int H,
                          int W, int penalty, bool channels_last, float grad_scale, modet_stream_t stream) {
   MODET_CHECK_DIM(penalty == 1 || penalty == 2);
   MODET_CHECK_PTR(flow); MODET_CHECK_PTR(loss); MODET_CHECK_PTR(ws);
   MODET_CHECK_DIM(B > 0 && D > 1 && H > 1 && W > 1);
-  if (ws_bytes < modet_grad3d_ws_bytes(B, D, H, W)) return MODET_ERR_WORKSPACE;
+  if (ws_bytes < modet_grad3d_ws_bytes(B, D, H, W) || ((uintptr_t)ws & 7) != 0) return MODET_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   const Dims d{channels_last ? B : B * 3, D, H, W};
   const int64_t N = (int64_t)B * 3 * D * H * W;
@@ -534,12 +551,12 @@ static int grad3d_launch(const float* flow, float* loss, float* d_flow, void* ws
   const float inW = (float)(1.0 / ((double)B * 3 * D * H * (W - 1)));
   const int rg = red_grid(N);
 #define GRAD3D_GO(L1_, CS_)                                                                                                 \
-  hipLaunchKernelGGL((grad3d_kernel<L1_, CS_>), dim3(rg), dim3(BLK), 0, s, flow, d_flow, (float*)ws, d, N, inD, inH, inW,  \
+  hipLaunchKernelGGL((grad3d_kernel<L1_, CS_>), dim3(rg), dim3(BLK), 0, s, flow, d_flow, (double*)ws, d, N, inD, inH, inW, \
                      grad_scale)
   if (penalty == 1) { if (channels_last) GRAD3D_GO(true, 3); else GRAD3D_GO(true, 1); }
   else { if (channels_last) GRAD3D_GO(false, 3); else GRAD3D_GO(false, 1); }
 #undef GRAD3D_GO
-  hipLaunchKernelGGL(scalar_finalize_kernel, dim3(1), dim3(BLK), 0, s, (const float*)ws, rg, 1.0 / 3.0, loss);
+  hipLaunchKernelGGL(scalar_finalize_kernel<double>, dim3(1), dim3(BLK), 0, s, (const double*)ws, rg, 1.0 / 3.0, loss);
   return modet_launch_status();
 }
 

@@ -1672,7 +1672,11 @@ class _NCC(Function):
         need_t, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         d_t = d_p = None
         if need_t and not need_p:
-            loss, d_t = _ncc_launch(y_pred, y_true, True, win)
+            # the VALUE always comes from the launch with the arguments in their own order: the kernel's expanded formula
+            # rounds differently with the roles swapped, and the value would depend (in its last bit) on which argument is
+            # differentiated
+            loss, _ = _ncc_launch(y_true, y_pred, False, win)
+            _, d_t = _ncc_launch(y_pred, y_true, True, win)
         else:
             loss, d_p = _ncc_launch(y_true, y_pred, need_p, win)
             if need_t:
