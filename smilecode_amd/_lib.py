@@ -175,6 +175,14 @@ REG_SIGNATURES = {
     "modet_reg_fwd_bwd": (I, [P, P, P, P, SZ, I, I, I, I, I, I, I, F, P]),
 }
 
+# scaling-and-squaring integration of a velocity field, a sixth table: mirrors include/modet_hip_vecint.h one to one, same library
+VECINT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "modet_hip_vecint.h")
+VECINT_SIGNATURES = {
+    "modet_vecint_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
+    "modet_vecint_ws_bytes": (SZ, [I, I, I, I, I, F]),
+    "modet_vecint_bwd": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, F, P]),
+}
+
 _lib = None
 
 
@@ -196,7 +204,8 @@ def load():
             "(the ModeT hot path has no CPU / eager fallback)")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(MI_SIGNATURES.items())
-                              + list(SSIM_SIGNATURES.items()) + list(REG_SIGNATURES.items())):
+                              + list(SSIM_SIGNATURES.items()) + list(REG_SIGNATURES.items())
+                              + list(VECINT_SIGNATURES.items())):
         if not hasattr(lib, name) and os.environ.get("MODET_HIP_LIB"):
             continue        # an older build loaded for A/B timing may predate an entry point; the product library may not
         fn = getattr(lib, name)

@@ -18,16 +18,22 @@ from .models import ModeT
 from .train import _natkey
 
 
-def main(argv=None):
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--val-dir", default="/LPBA_path/Val/")
     ap.add_argument("--model-dir", default="")
     ap.add_argument("--model-idx", type=int, default=-1)
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--img-size", default="160,192,160")
-    args = ap.parse_args(argv)
+    ap.add_argument("--diff", action="store_true", help="the diffeomorphic variant the checkpoint was trained with (train --diff)")
+    ap.add_argument("--int-steps", type=int, default=7, help="scaling-and-squaring steps of --diff")
+    return ap
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
     img_size = tuple(int(s) for s in args.img_size.split(","))
-    model = ModeT(img_size, head_dim=6, num_heads=[8, 4, 2, 1, 1], scale=1)
+    model = ModeT(img_size, head_dim=6, num_heads=[8, 4, 2, 1, 1], scale=1, diff=args.diff, int_steps=args.int_steps)
     if args.model_dir:
         files = sorted(os.listdir(args.model_dir), key=_natkey)
         # weights_only=False: checkpoints written by the reference's train.py carry numpy scalars (see train.py here)

@@ -80,6 +80,28 @@ class SpatialTransformer(nn.Module):
         return ops.warp(src_cl, flow_cl, 0 if self.mode == "bilinear" else 1, add_flow, flow_bound)
 
 
+class VecInt(nn.Module):
+    """Integrates a stationary velocity field by scaling and squaring (reference ModeT/models.py:70-87), NCDHW in / NCDHW out.
+
+    ``forward(vec)``: vec (B,3,D,H,W) in voxels -> (B,3,D,H,W).  No parameters; ``transformer`` is the reference's attribute, so
+    with ``legacy_grid_buffers=True`` the state dict carries ``transformer.grid`` as the reference's does.  ``bound`` (forward_cl)
+    is ops.vecint's promise max |vec| <= bound."""
+
+    def __init__(self, inshape, nsteps=7, legacy_grid_buffers=False):
+        super().__init__()
+        if isinstance(nsteps, bool) or not isinstance(nsteps, int) or not 0 <= nsteps <= ops.VECINT_MAX_STEPS:
+            raise RuntimeError(f"VecInt: nsteps must be an integer in 0..{ops.VECINT_MAX_STEPS}, got {nsteps!r}")
+        self.nsteps = nsteps
+        self.scale = 1.0 / (2 ** self.nsteps)
+        self.transformer = SpatialTransformer(inshape, legacy_grid_buffers=legacy_grid_buffers)
+
+    def forward(self, vec):
+        return ops.to_ncdhw(self.forward_cl(ops.to_channels_last(vec.contiguous())))
+
+    def forward_cl(self, vec_cl, bound=0.0):
+        return ops.vecint(vec_cl, self.nsteps, bound)
+
+
 class _Conv3dParams(nn.Module):
     """parameter holder with nn.Conv3d's names, shapes and default init (weight (Cout,Cin,3,3,3), bias)."""
 
@@ -417,8 +439,11 @@ class ModeT(nn.Module):
     stage_cuts = False      # set by engine.Trainer around a forward whose backward runs in stages
 
     def __init__(self, inshape=(160, 192, 160), in_channel=1, channels=4, head_dim=6, num_heads=[8, 4, 2, 1, 1],
-                 scale=None, legacy_grid_buffers=False, act_dtype=torch.float32, fused_attention=True):
-        """``act_dtype=torch.bfloat16`` (not in the reference, BASELINE.json configs[4]): the encoder's ConvInsBlock chains
+                 scale=None, legacy_grid_buffers=False, act_dtype=torch.float32, fused_attention=True, diff=False, int_steps=7):
+        """``diff=True`` (not in the reference's ModeT; its RDN_diff models, Baseline methods/RDN/models.py:268-310): every level's
+        field is integrated by ``int_steps`` steps of scaling and squaring (VecInt) before it is composed.  No new tensors:
+        checkpoints are interchangeable between the two modes.
+        ``act_dtype=torch.bfloat16`` (not in the reference, BASELINE.json configs[4]): the encoder's ConvInsBlock chains
         store their activations in bf16 and run on the bf16 matrix pipe with fp32 accumulation; parameters, statistics,
         level features, flows, losses and the optimizer stay fp32, so checkpoints are unchanged; each level's warped moving
         features and its q / k projections -- tensors only the level's own matching step reads -- are stored as bf16 too
@@ -451,6 +476,8 @@ class ModeT(nn.Module):
             raise RuntimeError("ModeT: inshape = (D, H, W)")
         self.channels = channels
         self.step = 7
+        self.diff = bool(diff)
+        self.int_steps = int_steps
         self.inshape = tuple(inshape)
         c = channels
         fl = self._flavour
@@ -474,6 +501,10 @@ class ModeT(nn.Module):
         self.transformer = nn.ModuleList(
             [SpatialTransformer([s // 2 ** i for s in inshape], legacy_grid_buffers=legacy_grid_buffers)
              for i in range(4)])
+        # level i + 1's integration (diff=True only; VecInt has no tensors, so the state dict is the same in both modes), at the
+        # resolution of the field it takes: levels 1 and 2 the attention output, levels 3 to 5 the x2-upsampled CWM output
+        self.integrate = nn.ModuleList(
+            [VecInt([s // f for s in inshape], int_steps) for f in (1, 2, 2, 4, 8)]) if self.diff else None
 
     def forward(self, moving, fixed):
         """(y_moved (B,1,D,H,W), flow (B,3,D,H,W)) -- reference models.py:380-412"""
@@ -505,6 +536,14 @@ class ModeT(nn.Module):
             Fx = [ops.feature_handle_like(f.detach().requires_grad_(True), f) for f in Fx]
             self.cut_leaves = (M, Fx)
         ST = self.transformer
+        # diff=True: w -> VecInt(w) before every composition, as RDN_diff does.  Levels 1 and 2 hand over bound=1 (their w is an
+        # expectation over offsets in {-1,0,1}^3), levels 3 to 5 (CWM outputs) no bound.  The flow_bound=1 compositions below
+        # stay valid: trilinear sampling with zeros padding is a convex combination of values and zeros, so a step at most
+        # doubles the maximum, max |v_{k+1}| <= 2 max |v_k|, and from v_0 = w / 2^n follows max |VecInt(w)| <= max |w| <= 1.
+        if self.diff:
+            integ = lambda lvl, w, bound=0.0: self.integrate[lvl].forward_cl(w, bound)
+        else:
+            integ = lambda lvl, w, bound=0.0: w
 
         def match(lvl, proj, mdt, flow):
             """the level's matching step: attention(proj(F), proj(warp(M, flow))) -> (expected offset field, flow).  The
@@ -525,25 +564,27 @@ class ModeT(nn.Module):
             return mdt(q, k), flow
 
         with ops.trace_range("level5"):
-            flow = self.cwm5(match(4, self.projblock5, self.mdt5, None)[0])
+            flow = integ(4, self.cwm5(match(4, self.projblock5, self.mdt5, None)[0]))
 
         with ops.trace_range("level4"):
             field, flow = match(3, self.projblock4, self.mdt4, flow)
-            w = self.cwm4(field)
+            w = integ(3, self.cwm4(field))
             flow = ST[2].forward_cl(ops.upsample2(flow, 2.0), w, add_flow=True)
 
         with ops.trace_range("level3"):
             field, flow = match(2, self.projblock3, self.mdt3, flow)
-            w = self.cwm3(field)
+            w = integ(2, self.cwm3(field))
             flow = ST[1].forward_cl(ops.upsample2(flow, 2.0), w, add_flow=True)
 
         with ops.trace_range("level2"):
             w, flow = match(1, self.projblock2, self.mdt2, flow)
+            w = integ(1, w, 1.0)
             # w comes straight from the attention (expected offset in [-1,1]^3): bounded-flow backward, no atomics
             flow = ops.upsample2(ST[1].forward_cl(flow, w, add_flow=True, flow_bound=1), 2.0)
 
         with ops.trace_range("level1"):
             w, flow = match(0, self.projblock1, self.mdt1, flow)
+            w = integ(0, w, 1.0)
             flow = ST[0].forward_cl(flow, w, add_flow=True, flow_bound=1)
             y_moved, flow = ops.warp_tee(mov_cl, flow)      # (the flow's other consumer: the caller, Grad3d in training)
         return y_moved, flow
@@ -555,9 +596,9 @@ class ModeT_cu(ModeT):
     _flavour = "v"
 
     def __init__(self, inshape=(160, 192, 160), in_channel=1, channels=4, head_dim=6, num_heads=[8, 4, 2, 1, 1],
-                 scale=1, legacy_grid_buffers=False, act_dtype=torch.float32, fused_attention=True):
+                 scale=1, legacy_grid_buffers=False, act_dtype=torch.float32, fused_attention=True, diff=False, int_steps=7):
         super().__init__(inshape, in_channel, channels, head_dim, num_heads, scale, legacy_grid_buffers, act_dtype,
-                         fused_attention)
+                         fused_attention, diff, int_steps)
 
 
 def load_numpy_weights(model: nn.Module, weights) -> None:

@@ -2036,6 +2036,99 @@ def reg_loss(flow, kind):
     return _Reg.apply(flow, kind)
 
 
+# ------------------------------------------------------------------------------------------------ velocity-field integration
+VECINT_MAX_STEPS = 12       # MODET_VECINT_MAX_STEPS of include/modet_hip_vecint.h
+
+
+def _vecint_args(op, vec, nsteps, bound):
+    """(B, D, H, W) of a channels-last (B,D,H,W,3) fp32 field; nsteps and bound in the library's range"""
+    if isinstance(nsteps, bool) or not isinstance(nsteps, int) or not 0 <= nsteps <= VECINT_MAX_STEPS:
+        raise RuntimeError(f"{op}: nsteps must be an integer in 0..{VECINT_MAX_STEPS}, got {nsteps!r}")
+    bound = float(bound)
+    if not (0.0 <= bound < float("inf")):
+        raise RuntimeError(f"{op}: bound must be finite and >= 0 (0 = no promise on max |vec|), got {bound!r}")
+    _chk(vec)
+    _rank5(op, "vec", vec)
+    B, D, H, W, C = vec.shape
+    if C != 3:
+        raise RuntimeError(f"{op}: vec must be a channels-last (B,D,H,W,3) field, got {tuple(vec.shape)}")
+    if min(B, D, H, W) < 1 or vec.numel() >= 2 ** 31:
+        raise RuntimeError(f"{op}: vec {tuple(vec.shape)} must be non-empty and hold fewer than 2^31 elements")
+    return B, D, H, W
+
+
+def _vecint_general_steps(nsteps, bound):
+    """how many of the backward's steps take the scatter path (include/modet_hip_vecint.h: bound * 2^(k - nsteps) > 1, or no bound)"""
+    return sum(1 for k in range(nsteps) if not (bound > 0.0 and bound * 2.0 ** (k - nsteps) <= 1.0))
+
+
+def _vecint_fwd(vec, nsteps, want_steps):
+    """modet_vecint_fwd -> (out, steps or None).  Per voxel and step, this implementation's own count: the footprint (3 floors, 3
+    fractions, 8 weights of 2 products) and 8 corners x 3 channels of a masked fma, ~80 FLOP; the field read once and written once
+    (12 + 12 B; the corner reads are served by the caches)."""
+    B, D, H, W = vec.shape[:4]
+    out = torch.empty_like(vec)
+    steps = scratch = None
+    if nsteps >= 2:
+        if want_steps:
+            steps = torch.empty((nsteps - 1,) + tuple(vec.shape), dtype=torch.float32, device=vec.device)
+        else:
+            scratch = torch.empty_like(vec)
+    n = float(B) * D * H * W
+    with _Guard(vec, f"vecint_fwd[n{nsteps}]", 80.0 * n * nsteps, 24.0 * n * max(nsteps, 1)):
+        _call(_L().modet_vecint_fwd, _p(vec), _p(out), _p(steps), _p(scratch), B, D, H, W, nsteps, _stream())
+    return out, steps
+
+
+def _vecint_bwd(vec, steps, dout, nsteps, bound):
+    """modet_vecint_bwd -> d_vec.  Per voxel and step: the 27-neighbour hat weights and their fma (27 x 14) plus the flow term
+    (8 corners x (5 + 9)) and the sum, ~500 FLOP bounded; a general step has the flow term and the sum (~130) beside the scatter's
+    own work, which is not counted here.  Bytes: v and g read, d_v written (36 B), a general step also writes and reads the
+    scattered sum (+ 24 B)."""
+    B, D, H, W = vec.shape[:4]
+    L = _L()
+    dvec = torch.empty_like(vec)
+    scratch = torch.empty_like(vec) if nsteps >= 2 else None
+    nb = L.modet_vecint_ws_bytes(B, D, H, W, nsteps, bound)
+    ng = _vecint_general_steps(nsteps, bound)
+    if ng and not nb:
+        raise RuntimeError(f"vecint: field {tuple(vec.shape)} is out of the kernels' range")
+    ws = _ws(nb, vec) if nb else None
+    n = float(B) * D * H * W
+    with _Guard(vec, f"vecint_bwd[n{nsteps},g{ng}]", n * (500.0 * (nsteps - ng) + 130.0 * ng),
+                n * (36.0 * max(nsteps, 1) + 24.0 * ng)):
+        _call(L.modet_vecint_bwd, _p(vec), _p(steps), _p(dout), _p(dvec), _p(scratch), _p(ws), nb, B, D, H, W, nsteps, bound,
+              _stream())
+    return dvec
+
+
+class _VecInt(Function):
+    """saves vec and the inputs of steps 1 .. nsteps-1 (the input of step 0 is recomputed from vec)"""
+
+    @staticmethod
+    def forward(ctx, vec, nsteps, bound):
+        out, steps = _vecint_fwd(vec, nsteps, ctx.needs_input_grad[0])
+        ctx.save_for_backward(vec, steps)
+        ctx.nsteps, ctx.bound = nsteps, bound
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        vec, steps = ctx.saved_tensors
+        dout = dout.contiguous()
+        _chk(dout)
+        return _vecint_bwd(vec, steps, dout, ctx.nsteps, ctx.bound), None, None
+
+
+def vecint(flow_cl, nsteps=7, bound=0.0):
+    """VecInt(nsteps) of a channels-last (B,D,H,W,3) velocity field in voxels: v = vec / 2^nsteps, then nsteps times
+    v = v + sample(v, p + v) (reference: models.py:70-87).  bound > 0 promises max |vec| <= bound: the backward of every step whose
+    field is then bounded by one voxel (bound * 2^(k - nsteps) <= 1) is one gather without atomics.  A broken promise may give a
+    wrong gradient, never an out-of-range access."""
+    _vecint_args("vecint", flow_cl, nsteps, bound)
+    return _VecInt.apply(flow_cl, nsteps, float(bound))
+
+
 # ------------------------------------------------------------------------------------------------ non-autograd
 def ncc_value_and_grad(y_true, y_pred, win=9, grad_scale=1.0):
     """(NCC_vxm(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call -- no autograd node: the

@@ -97,15 +97,20 @@ def make_parser():
                          "DisplacementRegularizer's central-difference gradient norms (gradient-l2, gradient-l1) or bending energy "
                          "(bending), the usual partner of mi and mind")
     ap.add_argument("--reg-weight", type=float, default=1, help="weight of the regulariser in the loss (the reference's weights[1])")
+    ap.add_argument("--diff", action="store_true",
+                    help="diffeomorphic variant: every level's field is integrated by scaling and squaring (VecInt) before it is "
+                         "composed, as the reference's RDN_diff models do; same parameters, so checkpoints are interchangeable")
+    ap.add_argument("--int-steps", type=int, default=7, help="scaling-and-squaring steps of --diff (the reference's VecInt default)")
     return ap
 
 
 def save_dir_name(args, num_heads, head_dim, weights):
     """the experiment directory: the reference's name (train.py:66-68) with the similarity term in it; a regulariser other than
-    the default Grad3d with weight 1 is named too, the default leaves the name as it always was"""
+    the default Grad3d with weight 1 is named too, the default leaves the name as it always was; --diff adds a suffix"""
     reg = "" if (args.reg == "grad3d" and weights[1] == 1) else "{}_".format(args.reg)
-    return "modet-heads({}{}{}{}{})-rpe_headim_{}_{}_{}_reg_{}{}_lr_{}_54r/".format(*num_heads, head_dim, args.sim, weights[0], reg,
-                                                                                   weights[1], args.lr)
+    diff = "_diff{}".format(args.int_steps) if getattr(args, "diff", False) else ""
+    return "modet-heads({}{}{}{}{})-rpe_headim_{}_{}_{}_reg_{}{}_lr_{}_54r{}/".format(*num_heads, head_dim, args.sim, weights[0], reg,
+                                                                                     weights[1], args.lr, diff)
 
 
 def main(argv=None):
@@ -126,7 +131,7 @@ def main(argv=None):
         sys.stdout = Logger(log_dir)
         f = open(os.path.join(log_dir, "losses and dice.txt"), "a")
 
-    model = ModeT(img_size, head_dim=head_dim, num_heads=num_heads, scale=1).cuda()
+    model = ModeT(img_size, head_dim=head_dim, num_heads=num_heads, scale=1, diff=args.diff, int_steps=args.int_steps).cuda()
     best_dsc = 0
     resume = None
     if args.cont_training:
