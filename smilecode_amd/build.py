@@ -80,7 +80,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("modet_hip.h", "modet_hip_losses.h", "modet_hip_mi.h", "modet_hip_ssim.h", "modet_hip_reg.h", "modet_hip_vecint.h")]
+    include = os.path.join(os.path.dirname(HERE), "include")
+    headers += [os.path.join(include, h) for h in sorted(os.listdir(include)) if h.endswith(".h")]
     jobs = []
     objs = []
     for src in SOURCES:

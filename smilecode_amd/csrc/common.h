@@ -85,6 +85,43 @@ __device__ __forceinline__ float block_sum(float v, float* smem /* >= 16 floats 
   return r;
 }
 
+// The fixed-order fp64 sums behind every loss value: no atomics, the same additions in the same order on every run, so a value
+// is bit-reproducible and its launches can be captured into a hipGraph.  Both for 1-D workgroups of NT threads (a multiple of 64).
+//
+// Workgroup sum of one double per thread: wave_sum_d, then LDS, then thread 0 adds the waves in wave order.  Valid in thread 0.
+template <int NT>
+__device__ __forceinline__ double block_sum_d(double v, double* red /* [NT / 64] shared */) {
+  v = wave_sum_d(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double r = 0.0;
+  if (threadIdx.x == 0)
+    for (int k = 0; k < NT / 64; ++k) r += red[k];
+  return r;
+}
+
+// Sum of the n partials of a whole launch by ONE workgroup: thread t adds part[t], part[t + NT], ... in fp64, then thread 0 adds
+// the NT thread sums in index order.  Valid in thread 0.
+template <int NT, typename T>
+__device__ __forceinline__ double fixed_order_sum(const T* __restrict__ part, int n, double* sm /* [NT] shared */) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += NT) s += (double)part[i];
+  sm[threadIdx.x] = s;
+  __syncthreads();
+  double r = 0.0;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < NT; ++i) r += sm[i];
+  return r;
+}
+
+// loss[0] = scale * sum(part[0..n)), one workgroup of 256 threads; part in fp32 or fp64
+template <typename T>
+static __global__ void scalar_finalize_kernel(const T* __restrict__ part, int n, double scale, float* __restrict__ loss) {
+  __shared__ double sm[256];
+  const double r = fixed_order_sum<256>(part, n, sm);
+  if (threadIdx.x == 0) loss[0] = (float)(r * scale);
+}
+
 // Column sums of a row-major [rows][ncol] float matrix over the rows [r0, r1), by one 256-thread workgroup, in fp64:
 // thread t reads element t of each group of 256/ncol consecutive rows (fully coalesced), four independent
 // accumulators, then a fixed-order sum over the row lanes.  out[ncol] is written by threads < ncol.  ncol <= 256.

@@ -295,22 +295,6 @@ inline MarchPlan march_plan(int B, int D, int H, int W, int win) {
   return p;
 }
 
-
-// loss[0] = scale * sum(part[0..n))  (fp64, fixed order); part in fp32 (NCC) or fp64 (Grad3d)
-template <typename T>
-__global__ void scalar_finalize_kernel(const T* __restrict__ part, int n, double scale, float* __restrict__ loss) {
-  __shared__ double sm[BLK];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += BLK) s += (double)part[i];
-  sm[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = 0.0;
-    for (int i = 0; i < BLK; ++i) r += sm[i];
-    loss[0] = (float)(r * scale);
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ NCC, any window
 // NCC_vxm(win=[wz, wy, wx]) for the windows the z-march kernel is not instantiated for -- even, anisotropic or > 9 voxels.
 // The reference pads EVERY axis by p = floor(win[0] / 2) (losses.py:57), so the five window sums live on a grid of
@@ -392,7 +376,7 @@ constexpr int NCC_BOX_PARTS = 1024;
 // (losses.py:11-27); the gradient of |t| at t = 0 is 0, as torch.abs's backward (sign(0) = 0).  df = gscale * d loss / d f
 // (gscale = the loss term's weight, train.py:127-129; the product with 1.0f is exact).
 // The loss: every element contributes ONE fp32 value (its three forward terms, the same bits in either layout) and those are
-// summed in fp64 (per thread, per workgroup, then scalar_finalize_kernel), as csrc/reg.hip does -- which elements a thread or a
+// summed in fp64 (per thread, block_sum_d per workgroup, then scalar_finalize_kernel: common.h), as csrc/reg.hip does -- which elements a thread or a
 // workgroup holds depends on the layout, and fp32 partial sums made the planar and the channels-last value differ in the last
 // bit on small flows.
 template <bool L1, int CS>
@@ -427,14 +411,8 @@ __global__ __launch_bounds__(BLK) void grad3d_kernel(const float* __restrict__ f
     lsum += (double)e;
     if (df) df[i] = (g * (L1 ? 1.f / 3.f : 2.f / 3.f)) * gscale;
   }
-  lsum = wave_sum_d(lsum);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = 0.0;
-    for (int k = 0; k < BLK / 64; ++k) r += red[k];
-    part[blockIdx.x] = r;
-  }
+  const double r = block_sum_d<BLK>(lsum, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
 inline int red_grid(int64_t N) {

@@ -185,29 +185,11 @@ __global__ __launch_bounds__(BLK) void mind_ssd_kernel(const float* __restrict__
 // bnd[0] = 0.001 g, bnd[1] = 1000 g with g = sum(part) / N: fp64, fixed order, one workgroup
 __global__ __launch_bounds__(BLK) void mind_bounds_kernel(const float* __restrict__ part, int n, double inv_n, float* __restrict__ bnd) {
   __shared__ double sm[BLK];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += BLK) s += (double)part[i];
-  sm[threadIdx.x] = s;
-  __syncthreads();
+  const double r = fixed_order_sum<BLK>(part, n, sm);
   if (threadIdx.x == 0) {
-    double r = 0.0;
-    for (int i = 0; i < BLK; ++i) r += sm[i];
     const float g = (float)(r * inv_n);
     bnd[0] = g * 0.001f;
     bnd[1] = g * 1000.f;
-  }
-}
-
-__global__ __launch_bounds__(BLK) void mind_scalar_kernel(const float* __restrict__ part, int n, double scale, float* __restrict__ out) {
-  __shared__ double sm[BLK];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += BLK) s += (double)part[i];
-  sm[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = 0.0;
-    for (int i = 0; i < BLK; ++i) r += sm[i];
-    out[0] = (float)(r * scale);
   }
 }
 
@@ -451,7 +433,7 @@ int modet_mind_fwd_bwd(const float* a, const float* b, float* loss, float* d_b, 
   else
     hipLaunchKernelGGL((mind_point_kernel<false>), dim3(p.pgrid), dim3(BLK), 0, s, (const float*)ma, mb, (const float*)bnd, part_l, p.N,
                        p.N / B, gcoef);
-  hipLaunchKernelGGL(mind_scalar_kernel, dim3(1), dim3(BLK), 0, s, (const float*)part_l, p.pgrid, 1.0 / n_all, loss);
+  hipLaunchKernelGGL(scalar_finalize_kernel<float>, dim3(1), dim3(BLK), 0, s, (const float*)part_l, p.pgrid, 1.0 / n_all, loss);
   if (d_b) {
     float* F = ma;                                // m(a) is consumed: its first six volumes per sample take F
     hipLaunchKernelGGL(mind_adjoint_kernel, dim3(p.tiles), dim3(BLK), 0, s, (const float*)mb, b, F, d, p.tiles_x, p.tiles_y, p.tiles_z);

@@ -2,7 +2,7 @@
 // DisplacementRegularizer (:223-268) 'gradient-l2' (1), 'gradient-l1' (2) and 'bending' (3); include/modet_hip_reg.h has the formulae.
 //
 // One forward + backward launch per call (reg_kernel) and a fixed-order fp64 sum of the workgroups' loss partials
-// (reg_finalize_kernel).  Every kind is a streaming stencil in grad3d_kernel's scheme: a flat index over the ELEMENTS of the flow
+// (scalar_finalize_kernel, common.h).  Every kind is a streaming stencil in grad3d_kernel's scheme: a flat index over the ELEMENTS of the flow
 // in either layout (planar: CS = 1 over B C volumes; channels-last: CS = 3, a voxel's neighbours are CS elements apart), each thread
 // GATHERS the adjoint of the stencils that touch its element, so nothing is scattered, nothing is atomic and no intermediate volume
 // exists: the flow is read (neighbours through the caches) and the gradient written once, 8 B per element.  A neighbour outside the
@@ -176,28 +176,8 @@ __global__ __launch_bounds__(BLK) void reg_kernel(const float* __restrict__ f, f
     lsum += (double)t.loss;
     if (df) df[i] = t.grad * gcoef;
   }
-  lsum = wave_sum_d(lsum);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = 0.0;
-    for (int k = 0; k < BLK / 64; ++k) r += red[k];
-    part[blockIdx.x] = r;
-  }
-}
-
-// loss[0] = scale * sum(part[0..n))  (fp64, fixed order)
-__global__ void reg_finalize_kernel(const double* __restrict__ part, int n, double scale, float* __restrict__ loss) {
-  __shared__ double sm[BLK];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += BLK) s += part[i];
-  sm[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = 0.0;
-    for (int i = 0; i < BLK; ++i) r += sm[i];
-    loss[0] = (float)(r * scale);
-  }
+  const double r = block_sum_d<BLK>(lsum, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
 struct Plan { int64_t N; double M; int grid; };
@@ -257,7 +237,7 @@ int modet_reg_fwd_bwd(const float* f, float* loss, float* d_f, void* ws, size_t 
   }
 #undef REG_KIND
 #undef REG_GO
-  hipLaunchKernelGGL(reg_finalize_kernel, dim3(1), dim3(BLK), 0, s, (const double*)part, p.grid, lscale, loss);
+  hipLaunchKernelGGL(scalar_finalize_kernel<double>, dim3(1), dim3(BLK), 0, s, (const double*)part, p.grid, lscale, loss);
   return modet_launch_status();
 }
 

@@ -211,29 +211,16 @@ __global__ __launch_bounds__(BLK, 2) void ssim_march_kernel(const float* __restr
     }
   }
   if constexpr (FWD) {
-    lsum = wave_sum_d(lsum);
-    if ((tid & 63) == 0) red[tid >> 6] = lsum;
-    __syncthreads();
-    if (tid == 0) {
-      double r = 0.0;
-      for (int i = 0; i < BLK / 64; ++i) r += red[i];
-      part[blockIdx.x] = r;
-    }
+    const double r = block_sum_d<BLK>(lsum, red);
+    if (tid == 0) part[blockIdx.x] = r;
   }
 }
 
 // loss[0] = 1 - sum(part[0..n)) / count  (fp64, fixed order)
 __global__ void ssim_finalize_kernel(const double* __restrict__ part, int n, double count, float* __restrict__ loss) {
   __shared__ double sm[BLK];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += BLK) s += part[i];
-  sm[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = 0.0;
-    for (int i = 0; i < BLK; ++i) r += sm[i];
-    loss[0] = (float)(1.0 - r / count);
-  }
+  const double r = fixed_order_sum<BLK>(part, n, sm);
+  if (threadIdx.x == 0) loss[0] = (float)(1.0 - r / count);
 }
 
 inline bool window_ok(int w) { return w >= 1 && w <= MAX_WIN && (w & 1) == 1; }

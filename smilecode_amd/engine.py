@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import ops
-from .losses import SSIM3D, DisplacementRegularizer, Grad3d, Grad3DiTV, MIND_loss, MutualInformation, NCC_vxm, localMutualInformation
+from .losses import Grad3d, NCC_vxm, seeds
 from .parallel import FlatParams, broadcast_parameters
 
 
@@ -77,15 +77,11 @@ class Trainer:
     def _seedable(self):
         """the step's own loss path applies: the reference's two loss terms as the HIP kernels have them (cubic NCC window of
         3 / 5 / 7 / 9 voxels or one of the other similarity kernels; Grad3d without ``loss_mult``, Grad3DiTV or
-        DisplacementRegularizer -- exact types, a subclass keeps the autograd expression) on a model that hands out its
-        channels-last results"""
+        DisplacementRegularizer -- each term says so itself, losses.seeds: exact types, a subclass keeps the autograd
+        expression) on a model that hands out its channels-last results"""
         if not (self.seed_backward and hasattr(self.model, "forward_cl")):
             return False
-        if not ((type(self.reg) is Grad3d and self.reg.loss_mult is None) or type(self.reg) in (Grad3DiTV, DisplacementRegularizer)):
-            return False
-        if type(self.sim) in (MIND_loss, MutualInformation, localMutualInformation, SSIM3D):     # (the kernels differentiate y_moved)
-            return True
-        return type(self.sim) is NCC_vxm and len(set(self.sim._w)) == 1 and self.sim._w[0] in (3, 5, 7, 9)
+        return seeds(self.sim) and seeds(self.reg)
 
     def _seeded_loss(self, moving, fixed):
         """``loss`` for the step itself: ((loss, sim, reg) detached, roots, seeds) with ``seeds[i]`` = d loss / d ``roots[i]``
@@ -98,25 +94,8 @@ class Trainer:
         y_cl, flow_cl = self.model.forward_cl(moving, fixed)
         B, D, H, W, _ = y_cl.shape
         w0, w1 = float(self.weights[0]), float(self.weights[1])
-        if type(self.sim) is MIND_loss:
-            sim, d_y = ops.mind_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), w0)
-        elif type(self.sim) is MutualInformation:
-            s = self.sim
-            sim, d_y = ops.mi_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), s.sigma_ratio, s.minval,
-                                             s.maxval, s.num_bins, w0)
-        elif type(self.sim) is localMutualInformation:
-            s = self.sim
-            sim, d_y = ops.lmi_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), s.sigma_ratio, s.minval,
-                                              s.maxval, s.num_bins, s.patch_size, w0)
-        elif type(self.sim) is SSIM3D:
-            sim, d_y = ops.ssim_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), self.sim.window_size, w0)
-        else:
-            sim, d_y = ops.ncc_value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), self.sim._w[0], w0)
-        if type(self.reg) is Grad3d:
-            reg, d_flow = ops.grad3d_value_and_grad_cl(flow_cl.detach(), self.reg.penalty, w1)
-        else:
-            kind = "itv" if type(self.reg) is Grad3DiTV else self.reg.energy_type
-            reg, d_flow = ops.reg_value_and_grad_cl(flow_cl.detach(), kind, w1)
+        sim, d_y = self.sim.value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), w0)
+        reg, d_flow = self.reg.value_and_grad_cl(flow_cl.detach(), w1)
         if w0 != 1.0:
             sim = sim * w0
         if w1 != 1.0:

@@ -5,6 +5,8 @@ by those of csrc/mind.hip; ``MutualInformation`` and ``localMutualInformation`` 
 (the same file, 203-268) by those of csrc/reg.hip."""
 from __future__ import annotations
 
+from functools import partial
+
 import torch
 
 from . import ops
@@ -26,6 +28,12 @@ class Grad3d(torch.nn.Module):
             grad = grad * self.loss_mult
         return grad
 
+    def seedable(self):
+        return self.loss_mult is None
+
+    def value_and_grad_cl(self, flow_cl, grad_scale):
+        return ops.grad3d_value_and_grad_cl(flow_cl, self.penalty, grad_scale)
+
 
 class NCC_vxm(torch.nn.Module):
     """local normalized cross correlation loss over windows of ``win`` voxels (reference losses.py:34-94); ``win`` = None (the
@@ -45,6 +53,13 @@ class NCC_vxm(torch.nn.Module):
     def forward(self, y_true, y_pred):
         return ops.ncc_loss(y_true.contiguous(), y_pred.contiguous(), self._w)
 
+    def seedable(self):
+        """a cubic window of 3 / 5 / 7 / 9 voxels: what the scaled entry point has"""
+        return len(set(self._w)) == 1 and self._w[0] in (3, 5, 7, 9)
+
+    def value_and_grad(self, fixed, moved, grad_scale):
+        return ops.ncc_value_and_grad(fixed, moved, self._w[0], grad_scale)
+
 
 class MIND_loss(torch.nn.Module):
     """MIND-SSC descriptor distance (reference Baseline methods/RCN/losses.py:333-399): mean((MINDSSC(y_pred) - MINDSSC(y_true))^2)
@@ -54,28 +69,18 @@ class MIND_loss(torch.nn.Module):
         super().__init__()
         self.win = win
 
-    @staticmethod
-    def _check(y_pred, y_true):
-        for name, t in (("y_pred", y_pred), ("y_true", y_true)):
-            if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
-                raise RuntimeError(f"MIND_loss: {name} must be a non-empty (B,1,D,H,W) volume, got {tuple(t.shape)}")
-        if y_pred.shape != y_true.shape:
-            raise RuntimeError(f"MIND_loss: y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} differ in shape")
-
     def MINDSSC(self, img, radius=2, dilation=2):
         return ops.mind_ssc(img.contiguous(), radius, dilation)
 
     def forward(self, y_pred, y_true):
-        self._check(y_pred, y_true)
+        ops._pair_shapes("MIND_loss", y_pred, y_true, "y_pred", "y_true")
         return ops.mind_loss(y_pred.contiguous(), y_true.contiguous())
 
+    def seedable(self):
+        return True
 
-def _mi_check(name, y_true, y_pred):
-    for arg, t in (("y_true", y_true), ("y_pred", y_pred)):
-        if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
-            raise RuntimeError(f"{name}: {arg} must be a non-empty (B,1,D,H,W) volume, got {tuple(t.shape)}")
-    if y_pred.shape != y_true.shape:
-        raise RuntimeError(f"{name}: y_true {tuple(y_true.shape)} and y_pred {tuple(y_pred.shape)} differ in shape")
+    def value_and_grad(self, fixed, moved, grad_scale):
+        return ops.mind_value_and_grad(fixed, moved, grad_scale)
 
 
 class _ParzenMI(torch.nn.Module):
@@ -101,8 +106,14 @@ class MutualInformation(_ParzenMI):
         super().__init__(sigma_ratio, minval, maxval, num_bin)
 
     def forward(self, y_true, y_pred):
-        _mi_check("MutualInformation", y_true, y_pred)
+        ops._pair_shapes("MutualInformation", y_true, y_pred, "y_true", "y_pred")
         return ops.mi_loss(y_true.contiguous(), y_pred.contiguous(), self.sigma_ratio, self.minval, self.maxval, self.num_bins)
+
+    def seedable(self):
+        return True
+
+    def value_and_grad(self, fixed, moved, grad_scale):
+        return ops.mi_value_and_grad(fixed, moved, self.sigma_ratio, self.minval, self.maxval, self.num_bins, grad_scale)
 
 
 class localMutualInformation(_ParzenMI):
@@ -116,9 +127,16 @@ class localMutualInformation(_ParzenMI):
         self.patch_size = int(patch_size)
 
     def forward(self, y_true, y_pred):
-        _mi_check("localMutualInformation", y_true, y_pred)
+        ops._pair_shapes("localMutualInformation", y_true, y_pred, "y_true", "y_pred")
         return ops.lmi_loss(y_true.contiguous(), y_pred.contiguous(), self.sigma_ratio, self.minval, self.maxval, self.num_bins,
                             self.patch_size)
+
+    def seedable(self):
+        return True
+
+    def value_and_grad(self, fixed, moved, grad_scale):
+        return ops.lmi_value_and_grad(fixed, moved, self.sigma_ratio, self.minval, self.maxval, self.num_bins, self.patch_size,
+                                      grad_scale)
 
 
 def _ssim_check(name, img1, img2, window_size, size_average):
@@ -127,13 +145,8 @@ def _ssim_check(name, img1, img2, window_size, size_average):
                            "tensor)")
     if not (int(window_size) == window_size and 1 <= int(window_size) <= ops.SSIM_MAX_WINDOW and int(window_size) % 2 == 1):
         raise RuntimeError(f"{name}: window_size must be an odd integer in 1..{ops.SSIM_MAX_WINDOW}, got {window_size}")
-    if img1 is None:
-        return
-    for arg, t in (("img1", img1), ("img2", img2)):
-        if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
-            raise RuntimeError(f"{name}: {arg} must be a non-empty (B,1,D,H,W) volume, got {tuple(t.shape)}")
-    if img1.shape != img2.shape:
-        raise RuntimeError(f"{name}: img1 {tuple(img1.shape)} and img2 {tuple(img2.shape)} differ in shape")
+    if img1 is not None:
+        ops._pair_shapes(name, img1, img2, "img1", "img2")
 
 
 class SSIM3D(torch.nn.Module):
@@ -148,6 +161,12 @@ class SSIM3D(torch.nn.Module):
     def forward(self, img1, img2):
         _ssim_check("SSIM3D", img1, img2, self.window_size, self.size_average)
         return ops.ssim_loss(img1.contiguous(), img2.contiguous(), self.window_size)
+
+    def seedable(self):
+        return True
+
+    def value_and_grad(self, fixed, moved, grad_scale):
+        return ops.ssim_value_and_grad(fixed, moved, self.window_size, grad_scale)
 
 
 def ssim3D(img1, img2, window_size=11, size_average=True):
@@ -173,6 +192,12 @@ class Grad3DiTV(torch.nn.Module):
         _flow_check("Grad3DiTV", y_pred, "itv")
         return ops.reg_loss(y_pred.contiguous(), "itv")
 
+    def seedable(self):
+        return True
+
+    def value_and_grad_cl(self, flow_cl, grad_scale):
+        return ops.reg_value_and_grad_cl(flow_cl, "itv", grad_scale)
+
 
 class DisplacementRegularizer(torch.nn.Module):
     """'bending', 'gradient-l2' or 'gradient-l1' energy of a 3-channel displacement field from central differences on its
@@ -189,3 +214,23 @@ class DisplacementRegularizer(torch.nn.Module):
     def forward(self, disp, _=None):
         _flow_check("DisplacementRegularizer", disp, self.energy_type)
         return ops.reg_loss(disp.contiguous(), self.energy_type)
+
+    def seedable(self):
+        return True
+
+    def value_and_grad_cl(self, flow_cl, grad_scale):
+        return ops.reg_value_and_grad_cl(flow_cl, self.energy_type, grad_scale)
+
+
+def seeds(term):
+    """the step may start its backward from the term's own gradient (``value_and_grad`` of a similarity term,
+    ``value_and_grad_cl`` of a regulariser): the term is, by exact type, one of the classes of SIM_TERMS / REG_TERMS below, and
+    says that this configuration is seedable.  A subclass or a foreign module goes through autograd."""
+    known = set(SIM_TERMS.values()) | {getattr(make, "func", make) for make in REG_TERMS.values()}
+    return type(term) in known and term.seedable()
+
+
+# the terms by the names train.py's --sim and --reg know: name -> what builds the term with the script's settings
+SIM_TERMS = {"ncc": NCC_vxm, "mind": MIND_loss, "mi": MutualInformation, "lmi": localMutualInformation, "ssim": SSIM3D}
+REG_TERMS = {"grad3d": partial(Grad3d, penalty="l2"), "itv": Grad3DiTV, "gradient-l2": partial(DisplacementRegularizer, "gradient-l2"),
+             "gradient-l1": partial(DisplacementRegularizer, "gradient-l1"), "bending": partial(DisplacementRegularizer, "bending")}

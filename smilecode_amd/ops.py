@@ -1634,61 +1634,107 @@ def _scale_by(x, s):
     return y
 
 
-def _ncc_launch(I, J, want_grad, win=9):
-    """modet_ncc_fwd_bwd_win(I, J): (loss (1,), d loss / d J or None); win = 3 | 5 | 7 | 9 (cubic: the z-marching kernel) or a
-    tuple (wz, wy, wx) of any positive sizes (modet_ncc_fwd_bwd_box: the reference's padding rule, separable sums)"""
-    B, _, D, H, W = I.shape
-    loss = torch.empty(1, dtype=torch.float32, device=I.device)
-    dJ = torch.empty_like(J) if want_grad else None
-    L = _L()
-    if isinstance(win, tuple):
-        wz, wy, wx = win
-        nb = L.modet_ncc_box_ws_bytes(B, D, H, W, wz, wy, wx)
-        if nb == 0:
-            raise RuntimeError(f"NCC: window {list(win)} leaves no output voxel on a {(D, H, W)} volume")
-        ws = _ws(nb, I)
-        nv = float(I.numel())
-        with _Guard(I, "ncc_fwd_bwd_box", 30.0 * (wz + wy + wx) * nv, 150.0 * nv):
-            _call(L.modet_ncc_fwd_bwd_box, _p(I), _p(J), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, wz, wy, wx, _stream())
-        return loss, dJ
-    nb = L.modet_ncc_ws_bytes(B, D, H, W)
-    ws = _ws(nb, I)
-    nv = float(I.numel())               # reads I,J once, writes d_J once
-    with _Guard(I, "ncc_fwd_bwd", 400.0 * nv, 12.0 * nv):
-        _call(L.modet_ncc_fwd_bwd_win, _p(I), _p(J), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, int(win), _stream())
-    return loss, dJ
+def _volume(op, name, t):
+    """one non-empty (B,1,D,H,W) volume"""
+    if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
+        raise RuntimeError(f"{op}: {name} must be a non-empty (B,1,D,H,W) volume, got {tuple(t.shape)}")
 
 
-class _NCC(Function):
-    """cc is symmetric in its two arguments (losses.py:85-93), so the gradient w.r.t. y_true is the kernel's d_J with
-    the roles swapped.  The reference's train loop differentiates the FIRST argument (train.py:127:
-    ``loss_function(output[n], y)`` = NCC_vxm.forward(y_true=y_moved, y_pred=fixed))."""
+def _pair_shapes(op, a, b, name_a, name_b):
+    """two volumes of equal shape -- the shapes alone: the module classes of losses.py name them on tensors they have yet to
+    make contiguous"""
+    _volume(op, name_a, a)
+    _volume(op, name_b, b)
+    if a.shape != b.shape:
+        raise RuntimeError(f"{op}: {name_b} {tuple(b.shape)} does not match {name_a} {tuple(a.shape)}: they differ in shape")
+
+
+def _volume_pair(op, a, b, name_a, name_b):
+    """what every similarity term takes: two non-empty float32 (B,1,D,H,W) volumes of equal shape, refused in that order (the
+    dtype is looked at before the shape is)"""
+    _chk(a, b)
+    _pair_shapes(op, a, b, name_a, name_b)
+
+
+def _loss_bufs(x, wants, nbytes, refused=None):
+    """what every loss call writes: (the (1,) loss, [a gradient like x or None per entry of wants], the workspace of a *_ws_bytes
+    query).  ``refused``: the term's error when the query answers 0 bytes (out of the kernels' range)"""
+    if refused and nbytes == 0:
+        raise RuntimeError(refused)
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    return loss, [torch.empty_like(x) if w else None for w in wants], _ws(nbytes, x)
+
+
+class _Similarity(Function):
+    """every similarity term: ``launch(a, b, want_a, want_b, grad_scale, **params) -> (loss (1,), d_a | None, d_b | None)`` yields
+    the value and whichever of the two gradients are needed; backward multiplies the saved gradients by the upstream scalar"""
 
     @staticmethod
-    def forward(ctx, y_true, y_pred, win=9):
-        _chk(y_true, y_pred)
-        if y_true.shape != y_pred.shape or y_true.dim() != 5 or y_true.shape[1] != 1:
-            raise RuntimeError("NCC: expects two (B,1,D,H,W) volumes")
-        need_t, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        d_t = d_p = None
-        if need_t and not need_p:
-            # the VALUE always comes from the launch with the arguments in their own order: the kernel's expanded formula
-            # rounds differently with the roles swapped, and the value would depend (in its last bit) on which argument is
-            # differentiated
-            loss, _ = _ncc_launch(y_true, y_pred, False, win)
-            _, d_t = _ncc_launch(y_pred, y_true, True, win)
-        else:
-            loss, d_p = _ncc_launch(y_true, y_pred, need_p, win)
-            if need_t:
-                _, d_t = _ncc_launch(y_pred, y_true, True, win)
-        ctx.save_for_backward(d_t, d_p)
+    def forward(ctx, a, b, launch, params):
+        loss, d_a, d_b = launch(a, b, ctx.needs_input_grad[0], ctx.needs_input_grad[1], 1.0, **params)
+        ctx.save_for_backward(d_a, d_b)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        d_t, d_p = ctx.saved_tensors
+        d_a, d_b = ctx.saved_tensors
         g = g.contiguous().reshape(1)
-        return (None if d_t is None else _scale_by(d_t, g)), (None if d_p is None else _scale_by(d_p, g)), None
+        return (None if d_a is None else _scale_by(d_a, g)), (None if d_b is None else _scale_by(d_b, g)), None, None
+
+
+class _FlowTerm(Function):
+    """every regulariser of one flow: ``launch(flow, *params, want_grad, grad_scale=1.0) -> (loss (1,), d_flow | None)``, as
+    _Similarity"""
+
+    @staticmethod
+    def forward(ctx, flow, launch, params):
+        loss, df = launch(flow, *params, ctx.needs_input_grad[0])
+        ctx.save_for_backward(df)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (df,) = ctx.saved_tensors
+        return (None if df is None else _scale_by(df, g.contiguous().reshape(1))), None, None
+
+
+# ------------------------------------------------------------------------------------------------ NCC, Grad3d
+def _ncc_once(I, J, want_grad, win, grad_scale=None):
+    """one call in the kernel's roles: (loss (1,), d loss / d J or None); win = 3 | 5 | 7 | 9 (cubic: the z-marching kernel,
+    modet_ncc_fwd_bwd_win, or with a grad_scale modet_ncc_fwd_bwd_win_scaled) or a tuple (wz, wy, wx) of any positive sizes
+    (modet_ncc_fwd_bwd_box: the reference's padding rule, separable sums)"""
+    B, _, D, H, W = I.shape
+    L = _L()
+    nv = float(I.numel())
+    if isinstance(win, tuple):
+        wz, wy, wx = win
+        nb = L.modet_ncc_box_ws_bytes(B, D, H, W, wz, wy, wx)
+        loss, (dJ,), ws = _loss_bufs(J, (want_grad,), nb, f"NCC: window {list(win)} leaves no output voxel on a {(D, H, W)} volume")
+        with _Guard(I, "ncc_fwd_bwd_box", 30.0 * (wz + wy + wx) * nv, 150.0 * nv):
+            _call(L.modet_ncc_fwd_bwd_box, _p(I), _p(J), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, wz, wy, wx, _stream())
+        return loss, dJ
+    nb = L.modet_ncc_ws_bytes(B, D, H, W)
+    loss, (dJ,), ws = _loss_bufs(J, (want_grad,), nb)
+    with _Guard(I, "ncc_fwd_bwd", 400.0 * nv, 12.0 * nv):               # reads I,J once, writes d_J once
+        if grad_scale is None:
+            _call(L.modet_ncc_fwd_bwd_win, _p(I), _p(J), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, int(win), _stream())
+        else:
+            _call(L.modet_ncc_fwd_bwd_win_scaled, _p(I), _p(J), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, int(win),
+                  float(grad_scale), _stream())
+    return loss, dJ
+
+
+def _ncc_launch(a, b, want_a, want_b, grad_scale, win=9, scaled=False):
+    """cc is symmetric in its two arguments (losses.py:85-93), so the gradient w.r.t. a is the kernel's d_J with the roles
+    swapped.  The VALUE always comes from the call with the arguments in their own order: the kernel's expanded formula rounds
+    differently with the roles swapped, and the value would depend (in its last bit) on which argument is differentiated -- a
+    third call when only a needs a gradient.  scaled: the entry point that multiplies the gradient by grad_scale (the autograd
+    node's backward does that itself).  The reference's train loop differentiates the FIRST argument (train.py:127:
+    ``loss_function(output[n], y)`` = NCC_vxm.forward(y_true=y_moved, y_pred=fixed))."""
+    gs = grad_scale if scaled else None
+    loss, d_b = _ncc_once(a, b, want_b, win, gs)
+    d_a = _ncc_once(b, a, True, win, gs)[1] if want_a else None
+    return loss, d_a, d_b
 
 
 def ncc_loss(y_true, y_pred, win=9):
@@ -1700,39 +1746,40 @@ def ncc_loss(y_true, y_pred, win=9):
             raise RuntimeError(f"NCC: a window is three positive sizes, got {win}")
     else:
         w = (int(win),) * 3
-    if w[0] == w[1] == w[2] and w[0] in (3, 5, 7, 9):
-        return _NCC.apply(y_true, y_pred, w[0])
-    return _NCC.apply(y_true, y_pred, w)
+    _volume_pair("NCC", y_true, y_pred, "y_true", "y_pred")
+    cubic = w[0] == w[1] == w[2] and w[0] in (3, 5, 7, 9)
+    return _Similarity.apply(y_true, y_pred, _ncc_launch, {"win": w[0] if cubic else w})
 
 
-class _Grad3d(Function):
-    @staticmethod
-    def forward(ctx, flow, penalty):
-        _chk(flow)
-        if flow.dim() != 5 or flow.shape[1] != 3:
-            raise RuntimeError("Grad3d: expects a (B,3,D,H,W) flow")
-        B, _, D, H, W = flow.shape
-        loss = torch.empty(1, dtype=torch.float32, device=flow.device)
-        df = torch.empty_like(flow) if ctx.needs_input_grad[0] else None
-        L = _L()
-        nb = L.modet_grad3d_ws_bytes(B, D, H, W)
-        ws = _ws(nb, flow)
-        with _Guard(flow, "grad3d_fwd_bwd", 20.0 * flow.numel(), 8.0 * flow.numel()):
-            _call(L.modet_grad3d_fwd_bwd, _p(flow), _p(loss), _p(df), _p(ws), nb, B, D, H, W, int(penalty), _stream())
-        ctx.save_for_backward(df)
-        return loss.reshape(())
+def _grad3d_args(flow, penalty, channels_last):
+    """(B, D, H, W) of a planar (B,3,D,H,W) or channels-last (B,D,H,W,3) flow"""
+    if penalty not in ("l1", "l2"):
+        raise RuntimeError(f"Grad3d: unknown penalty {penalty!r}")
+    _chk(flow)
+    if flow.dim() != 5 or flow.shape[-1 if channels_last else 1] != 3:
+        raise RuntimeError(f"Grad3d: expects a {'channels-last (B,D,H,W,3)' if channels_last else '(B,3,D,H,W)'} flow")
+    return (flow.shape[0],) + tuple(flow.shape[1:4] if channels_last else flow.shape[2:])
 
-    @staticmethod
-    def backward(ctx, g):
-        (df,) = ctx.saved_tensors
-        return _scale_by(df, g.contiguous().reshape(1)), None
+
+def _grad3d_launch(flow, penalty, dims, channels_last, want_grad, grad_scale=1.0):
+    """modet_grad3d_fwd_bwd (planar; the autograd node's backward scales) / modet_grad3d_fwd_bwd_cl (channels-last, scaled here):
+    (loss (1,), d loss / d flow in the flow's layout or None)"""
+    L = _L()
+    nb = L.modet_grad3d_ws_bytes(*dims)
+    loss, (df,), ws = _loss_bufs(flow, (want_grad,), nb)
+    pen = 1 if penalty == "l1" else 2
+    with _Guard(flow, "grad3d_fwd_bwd", 20.0 * flow.numel(), 8.0 * flow.numel()):
+        if channels_last:
+            _call(L.modet_grad3d_fwd_bwd_cl, _p(flow), _p(loss), _p(df), _p(ws), nb, *dims, pen, float(grad_scale), _stream())
+        else:
+            _call(L.modet_grad3d_fwd_bwd, _p(flow), _p(loss), _p(df), _p(ws), nb, *dims, pen, _stream())
+    return loss, df
 
 
 def grad3d_loss(flow, penalty="l2"):
     """Grad3d(penalty='l1' | 'l2') on a planar (B,3,D,H,W) flow.  reference: losses.py:6-31"""
-    if penalty not in ("l1", "l2"):
-        raise RuntimeError(f"Grad3d: unknown penalty {penalty!r}")
-    return _Grad3d.apply(flow, 1 if penalty == "l1" else 2)
+    dims = _grad3d_args(flow, penalty, False)
+    return _FlowTerm.apply(flow, _grad3d_launch, (penalty, dims, False))
 
 
 # ------------------------------------------------------------------------------------------------ MIND-SSC
@@ -1740,12 +1787,7 @@ MIND_BYTES_PER_VOXEL = 352.0     # modet_mind_fwd_bwd with a gradient, its own t
                                  # 48 + 4 + 24 box adjoint, 24 + 4 gather
 
 
-def _mind_args(op, *ts, radius=2, dilation=2):
-    _chk(*ts)
-    for t in ts:
-        if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
-            raise RuntimeError(f"{op}: expects non-empty (B,1,D,H,W) volumes, got {tuple(t.shape)}")
-        _same_shape(op, "second volume", t, ts[0].shape, "first volume")
+def _mind_params(op, radius, dilation):
     if int(radius) != 2 or int(dilation) != 2:
         raise RuntimeError(f"{op}: only radius 2 and dilation 2 exist (the reference hard-codes them), got {radius} and {dilation}")
 
@@ -1753,7 +1795,9 @@ def _mind_args(op, *ts, radius=2, dilation=2):
 def mind_ssc(img, radius=2, dilation=2):
     """the MIND-SSC descriptor (B,12,D,H,W) of a (B,1,D,H,W) image in the reference's channel order.
     reference: Baseline methods/RCN/losses.py:350-396 (MIND_loss.MINDSSC)"""
-    _mind_args("mind_ssc", img, radius=radius, dilation=dilation)
+    _chk(img)
+    _volume("mind_ssc", "img", img)
+    _mind_params("mind_ssc", radius, dilation)
     B, _, D, H, W = img.shape
     out = torch.empty((B, 12, D, H, W), dtype=torch.float32, device=img.device)
     L = _L()
@@ -1767,50 +1811,34 @@ def mind_ssc(img, radius=2, dilation=2):
     return out
 
 
-def _mind_launch(a, b, want_grad, grad_scale=1.0):
+def _mind_once(a, b, want_grad, grad_scale):
     """modet_mind_fwd_bwd(a, b): (loss (1,), grad_scale * d loss / d b or None)"""
     B, _, D, H, W = a.shape
-    loss = torch.empty(1, dtype=torch.float32, device=a.device)
-    d_b = torch.empty_like(b) if want_grad else None
     L = _L()
     nb = L.modet_mind_ws_bytes(B, D, H, W, 2)
-    if nb == 0:
-        raise RuntimeError(f"MIND: volume {tuple(a.shape)} is out of the kernels' range")
-    ws = _ws(nb, a)
+    loss, (d_b,), ws = _loss_bufs(b, (want_grad,), nb, f"MIND: volume {tuple(a.shape)} is out of the kernels' range")
     nv = float(a.numel())
     with _Guard(a, "mind_fwd_bwd", 1500.0 * nv, (MIND_BYTES_PER_VOXEL if want_grad else 200.0) * nv):
         _call(L.modet_mind_fwd_bwd, _p(a), _p(b), _p(loss), _p(d_b), _p(ws), nb, B, D, H, W, 2, 2, float(grad_scale), _stream())
     return loss, d_b
 
 
-class _MIND(Function):
+def _mind_launch(a, b, want_a, want_b, grad_scale):
     """the loss is symmetric in its two arguments, so the gradient w.r.t. the first is the kernel's d_b with the roles swapped
-    (as _NCC).  The value of the swapped call is the same sum in the same order: whichever call ran gives the loss."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        _mind_args("MIND", a, b)
-        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        d_a = d_b = None
-        if need_a and not need_b:
-            loss, d_a = _mind_launch(b, a, True)
-        else:
-            loss, d_b = _mind_launch(a, b, need_b)
-            if need_a:
-                _, d_a = _mind_launch(b, a, True)
-        ctx.save_for_backward(d_a, d_b)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        d_a, d_b = ctx.saved_tensors
-        g = g.contiguous().reshape(1)
-        return (None if d_a is None else _scale_by(d_a, g)), (None if d_b is None else _scale_by(d_b, g))
+    (as _ncc_launch).  The value of the swapped call is the same sum in the same order: whichever call ran gives the loss."""
+    loss = d_a = d_b = None
+    if want_b or not want_a:
+        loss, d_b = _mind_once(a, b, want_b, grad_scale)
+    if want_a:
+        l2, d_a = _mind_once(b, a, True, grad_scale)
+        loss = l2 if loss is None else loss
+    return loss, d_a, d_b
 
 
 def mind_loss(a, b):
     """mean((MIND-SSC(a) - MIND-SSC(b))^2) of two (B,1,D,H,W) volumes.  reference: Baseline methods/RCN/losses.py:398-399"""
-    return _MIND.apply(a, b)
+    _volume_pair("MIND", a, b, "first volume", "second volume")
+    return _Similarity.apply(a, b, _mind_launch, {})
 
 
 # ------------------------------------------------------------------------------------------------ mutual information
@@ -1824,11 +1852,7 @@ MI_BYTES_PER_PASS = 8.0
 
 
 def _mi_args(op, y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_size=None):
-    _chk(y_true, y_pred)
-    for t in (y_true, y_pred):
-        if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
-            raise RuntimeError(f"{op}: expects non-empty (B,1,D,H,W) volumes, got {tuple(t.shape)}")
-    _same_shape(op, "y_pred", y_pred, y_true.shape, "y_true")
+    _volume_pair(op, y_true, y_pred, "y_true", "y_pred")
     if int(num_bin) != MI_BINS:
         raise RuntimeError(f"{op}: only num_bin = {MI_BINS} exists, got {num_bin}")
     if not (float(maxval) > 0.0 and float(maxval) > float(minval) and float(sigma_ratio) > 0.0):
@@ -1836,19 +1860,15 @@ def _mi_args(op, y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_siz
                            f"sigma_ratio {sigma_ratio}")
     if patch_size is not None and not (int(patch_size) == patch_size and 1 <= int(patch_size) <= MI_MAX_PATCH):
         raise RuntimeError(f"{op}: patch_size must be an integer in 1..{MI_MAX_PATCH}, got {patch_size}")
+    return {"sigma_ratio": sigma_ratio, "minval": minval, "maxval": maxval, "patch_size": patch_size}
 
 
-def _mi_launch(a, b, want_a, want_b, sigma_ratio, minval, maxval, patch_size=None, grad_scale=1.0):
+def _mi_launch(a, b, want_a, want_b, grad_scale, sigma_ratio, minval, maxval, patch_size=None):
     """modet_mi_fwd_bwd / modet_lmi_fwd_bwd (patch_size given): (loss (1,), grad_scale * d loss / d a or None, the same for b)"""
     B, _, D, H, W = a.shape
-    loss = torch.empty(1, dtype=torch.float32, device=a.device)
-    d_a = torch.empty_like(a) if want_a else None
-    d_b = torch.empty_like(b) if want_b else None
     L = _L()
     nb = L.modet_mi_ws_bytes(B, D, H, W, 0 if patch_size is None else int(patch_size))
-    if nb == 0:
-        raise RuntimeError(f"mutual information: volume {tuple(a.shape)} is out of the kernels' range")
-    ws = _ws(nb, a)
+    loss, (d_a, d_b), ws = _loss_bufs(a, (want_a, want_b), nb, f"mutual information: volume {tuple(a.shape)} is out of the kernels' range")
     nv = float(a.numel())
     ngrad = int(bool(want_a)) + int(bool(want_b))
     with _Guard(a, "mi_fwd_bwd" if patch_size is None else "lmi_fwd_bwd", MI_FLOP_PER_PASS * (1 + ngrad) * nv,
@@ -1862,34 +1882,17 @@ def _mi_launch(a, b, want_a, want_b, sigma_ratio, minval, maxval, patch_size=Non
     return loss, d_a, d_b
 
 
-class _MI(Function):
-    """one launch yields the value and whichever of the two gradients are needed (the kernels differentiate either image or
-    both); backward multiplies the saved gradients by the upstream scalar"""
-
-    @staticmethod
-    def forward(ctx, a, b, sigma_ratio, minval, maxval, num_bin, patch_size):
-        _mi_args("lmi_loss" if patch_size is not None else "mi_loss", a, b, sigma_ratio, minval, maxval, num_bin, patch_size)
-        loss, d_a, d_b = _mi_launch(a, b, ctx.needs_input_grad[0], ctx.needs_input_grad[1], sigma_ratio, minval, maxval, patch_size)
-        ctx.save_for_backward(d_a, d_b)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        d_a, d_b = ctx.saved_tensors
-        g = g.contiguous().reshape(1)
-        return (None if d_a is None else _scale_by(d_a, g)), (None if d_b is None else _scale_by(d_b, g)), None, None, None, None, None
-
-
 def mi_loss(y_true, y_pred, sigma_ratio=1, minval=0.0, maxval=1.0, num_bin=32):
     """-mutual information of two (B,1,D,H,W) volumes over 32 Parzen-window bins, averaged over the batch.
     reference: Baseline methods/RCN/losses.py:401-457 (MutualInformation)"""
-    return _MI.apply(y_true, y_pred, sigma_ratio, minval, maxval, num_bin, None)
+    return _Similarity.apply(y_true, y_pred, _mi_launch, _mi_args("mi_loss", y_true, y_pred, sigma_ratio, minval, maxval, num_bin))
 
 
 def lmi_loss(y_true, y_pred, sigma_ratio=1, minval=0.0, maxval=1.0, num_bin=32, patch_size=5):
     """-mutual information per non-overlapping patch of patch_size^3 voxels of the zero-padded volumes, averaged over all patches.
     reference: Baseline methods/RCN/losses.py:459-556 (localMutualInformation)"""
-    return _MI.apply(y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_size)
+    return _Similarity.apply(y_true, y_pred, _mi_launch,
+                             _mi_args("lmi_loss", y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_size))
 
 
 # ------------------------------------------------------------------------------------------------ SSIM3D
@@ -1913,26 +1916,18 @@ def _ssim_counts(window, want_a, want_b):
 
 
 def _ssim_args(op, img1, img2, window_size):
-    _chk(img1, img2)
-    for t in (img1, img2):
-        if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
-            raise RuntimeError(f"{op}: expects non-empty (B,1,D,H,W) volumes, got {tuple(t.shape)}")
-    _same_shape(op, "img2", img2, img1.shape, "img1")
+    _volume_pair(op, img1, img2, "img1", "img2")
     if not (int(window_size) == window_size and 1 <= int(window_size) <= SSIM_MAX_WINDOW and int(window_size) % 2 == 1):
         raise RuntimeError(f"{op}: window_size must be an odd integer in 1..{SSIM_MAX_WINDOW}, got {window_size}")
+    return {"window_size": window_size}
 
 
-def _ssim_launch(a, b, want_a, want_b, window_size, grad_scale=1.0):
+def _ssim_launch(a, b, want_a, want_b, grad_scale, window_size):
     """modet_ssim_fwd_bwd: (loss (1,), grad_scale * d loss / d a or None, the same for b)"""
     B, _, D, H, W = a.shape
-    loss = torch.empty(1, dtype=torch.float32, device=a.device)
-    d_a = torch.empty_like(a) if want_a else None
-    d_b = torch.empty_like(b) if want_b else None
     L = _L()
     nb = L.modet_ssim_ws_bytes(B, D, H, W, int(window_size))
-    if nb == 0:
-        raise RuntimeError(f"ssim_loss: volume {tuple(a.shape)} is out of the kernels' range")
-    ws = _ws(nb, a)
+    loss, (d_a, d_b), ws = _loss_bufs(a, (want_a, want_b), nb, f"ssim_loss: volume {tuple(a.shape)} is out of the kernels' range")
     nv = float(a.numel())
     flop, nbytes = _ssim_counts(window_size, want_a, want_b)
     with _Guard(a, "ssim_fwd_bwd", flop * nv, nbytes * nv):
@@ -1941,28 +1936,10 @@ def _ssim_launch(a, b, want_a, want_b, window_size, grad_scale=1.0):
     return loss, d_a, d_b
 
 
-class _SSIM(Function):
-    """one call yields the value and whichever of the two gradients are needed; backward multiplies the saved gradients by the
-    upstream scalar"""
-
-    @staticmethod
-    def forward(ctx, a, b, window_size):
-        _ssim_args("ssim_loss", a, b, window_size)
-        loss, d_a, d_b = _ssim_launch(a, b, ctx.needs_input_grad[0], ctx.needs_input_grad[1], window_size)
-        ctx.save_for_backward(d_a, d_b)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        d_a, d_b = ctx.saved_tensors
-        g = g.contiguous().reshape(1)
-        return (None if d_a is None else _scale_by(d_a, g)), (None if d_b is None else _scale_by(d_b, g)), None
-
-
 def ssim_loss(img1, img2, window_size=11):
     """1 - mean SSIM of two (B,1,D,H,W) volumes under a zero-padded Gaussian window (sigma 1.5) of window_size^3 voxels, applied
     as three 1-D filters.  reference: Baseline methods/RCN/losses.py:103-126 (SSIM3D)"""
-    return _SSIM.apply(img1, img2, window_size)
+    return _Similarity.apply(img1, img2, _ssim_launch, _ssim_args("ssim_loss", img1, img2, window_size))
 
 
 # ------------------------------------------------------------------------------------------------ flow regularisers beside Grad3d
@@ -1999,41 +1976,21 @@ def _reg_args(op, flow, kind, channels_last):
 
 def _reg_launch(flow, kind, dims, channels_last, want_grad, grad_scale=1.0):
     """modet_reg_fwd_bwd: (loss (1,), grad_scale * d loss / d flow in the flow's layout or None)"""
-    B, C, D, H, W = dims
-    loss = torch.empty(1, dtype=torch.float32, device=flow.device)
-    df = torch.empty_like(flow) if want_grad else None
     L = _L()
-    nb = L.modet_reg_ws_bytes(REG_KINDS[kind], B, C, D, H, W)
-    if nb == 0:
-        raise RuntimeError(f"reg_loss: flow {tuple(flow.shape)} is out of the kernels' range")
-    ws = _ws(nb, flow)
+    nb = L.modet_reg_ws_bytes(REG_KINDS[kind], *dims)
+    loss, (df,), ws = _loss_bufs(flow, (want_grad,), nb, f"reg_loss: flow {tuple(flow.shape)} is out of the kernels' range")
     flop, nbytes = _REG_COUNTS[kind]
     with _Guard(flow, f"reg_fwd_bwd[{kind}]", flop * flow.numel(), (nbytes if want_grad else 4.0) * flow.numel()):
-        _call(L.modet_reg_fwd_bwd, _p(flow), _p(loss), _p(df), _p(ws), nb, REG_KINDS[kind], B, C, D, H, W, int(bool(channels_last)),
+        _call(L.modet_reg_fwd_bwd, _p(flow), _p(loss), _p(df), _p(ws), nb, REG_KINDS[kind], *dims, int(bool(channels_last)),
               float(grad_scale), _stream())
     return loss, df
-
-
-class _Reg(Function):
-    """like _Grad3d: the call writes value and gradient, backward multiplies the saved gradient by the upstream scalar"""
-
-    @staticmethod
-    def forward(ctx, flow, kind):
-        dims = _reg_args("reg_loss", flow, kind, False)
-        loss, df = _reg_launch(flow, kind, dims, False, ctx.needs_input_grad[0])
-        ctx.save_for_backward(df)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        (df,) = ctx.saved_tensors
-        return (None if df is None else _scale_by(df, g.contiguous().reshape(1))), None
 
 
 def reg_loss(flow, kind):
     """a regulariser of a planar flow: 'itv' (B,C,D,H,W), the isotropic total variation (reference Baseline methods/RCN/losses.py:
     203-221), or on (B,3,D,H,W) 'gradient-l2', 'gradient-l1' and 'bending' (the same file, 223-268)"""
-    return _Reg.apply(flow, kind)
+    dims = _reg_args("reg_loss", flow, kind, False)
+    return _FlowTerm.apply(flow, _reg_launch, (kind, dims, False))
 
 
 # ------------------------------------------------------------------------------------------------ velocity-field integration
@@ -2130,73 +2087,50 @@ def vecint(flow_cl, nsteps=7, bound=0.0):
 
 
 # ------------------------------------------------------------------------------------------------ non-autograd
+# (the term as a device scalar, grad_scale * d term / d its second argument, or its flow) from one call of the term's launch
+# function above -- no autograd node: the trainer seeds its backward with the gradient (engine.Trainer._seeded_loss)
+def _seed(launch, a, b, grad_scale, **params):
+    loss, _, d_b = launch(a, b, False, True, grad_scale, **params)
+    return loss.reshape(()), d_b
+
+
 def ncc_value_and_grad(y_true, y_pred, win=9, grad_scale=1.0):
     """(NCC_vxm(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call -- no autograd node: the
     trainer seeds its backward with the gradient (engine.Trainer._seeded_loss).  Cubic windows 3 / 5 / 7 / 9.
     reference: losses.py:34-94, train.py:127"""
-    _chk(y_true, y_pred)
-    if y_true.shape != y_pred.shape or y_true.dim() != 5 or y_true.shape[1] != 1:
-        raise RuntimeError("NCC: expects two (B,1,D,H,W) volumes")
-    B, _, D, H, W = y_true.shape
-    loss = torch.empty(1, dtype=torch.float32, device=y_true.device)
-    dJ = torch.empty_like(y_pred)
-    L = _L()
-    nb = L.modet_ncc_ws_bytes(B, D, H, W)
-    ws = _ws(nb, y_true)
-    nv = float(y_true.numel())
-    with _Guard(y_true, "ncc_fwd_bwd", 400.0 * nv, 12.0 * nv):
-        _call(L.modet_ncc_fwd_bwd_win_scaled, _p(y_true), _p(y_pred), _p(loss), _p(dJ), _p(ws), nb, B, D, H, W, int(win),
-              float(grad_scale), _stream())
-    return loss.reshape(()), dJ
+    _volume_pair("NCC", y_true, y_pred, "y_true", "y_pred")
+    return _seed(_ncc_launch, y_true, y_pred, grad_scale, win=int(win), scaled=True)
 
 
 def mind_value_and_grad(a, b, grad_scale=1.0):
     """(mind_loss(a, b) as a device scalar, grad_scale * d loss / d b) from one call -- no autograd node: the trainer seeds its
     backward with the gradient (engine.Trainer._seeded_loss)"""
-    _mind_args("MIND", a, b)
-    loss, d_b = _mind_launch(a, b, True, grad_scale)
-    return loss.reshape(()), d_b
+    _volume_pair("MIND", a, b, "first volume", "second volume")
+    return _seed(_mind_launch, a, b, grad_scale)
 
 
 def mi_value_and_grad(y_true, y_pred, sigma_ratio=1, minval=0.0, maxval=1.0, num_bin=32, grad_scale=1.0):
     """(mi_loss(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call -- no autograd node: the trainer
     seeds its backward with the gradient (engine.Trainer._seeded_loss)"""
-    _mi_args("mi_loss", y_true, y_pred, sigma_ratio, minval, maxval, num_bin)
-    loss, _, d_b = _mi_launch(y_true, y_pred, False, True, sigma_ratio, minval, maxval, None, grad_scale)
-    return loss.reshape(()), d_b
+    return _seed(_mi_launch, y_true, y_pred, grad_scale, **_mi_args("mi_loss", y_true, y_pred, sigma_ratio, minval, maxval, num_bin))
 
 
 def lmi_value_and_grad(y_true, y_pred, sigma_ratio=1, minval=0.0, maxval=1.0, num_bin=32, patch_size=5, grad_scale=1.0):
     """(lmi_loss(y_true, y_pred) as a device scalar, grad_scale * d loss / d y_pred) from one call, as mi_value_and_grad"""
-    _mi_args("lmi_loss", y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_size)
-    loss, _, d_b = _mi_launch(y_true, y_pred, False, True, sigma_ratio, minval, maxval, int(patch_size), grad_scale)
-    return loss.reshape(()), d_b
+    return _seed(_mi_launch, y_true, y_pred, grad_scale,
+                 **_mi_args("lmi_loss", y_true, y_pred, sigma_ratio, minval, maxval, num_bin, patch_size))
 
 
 def ssim_value_and_grad(img1, img2, window_size=11, grad_scale=1.0):
     """(ssim_loss(img1, img2) as a device scalar, grad_scale * d loss / d img2) from one call, as mi_value_and_grad"""
-    _ssim_args("ssim_loss", img1, img2, window_size)
-    loss, _, d_b = _ssim_launch(img1, img2, False, True, window_size, grad_scale)
-    return loss.reshape(()), d_b
+    return _seed(_ssim_launch, img1, img2, grad_scale, **_ssim_args("ssim_loss", img1, img2, window_size))
 
 
 def grad3d_value_and_grad_cl(flow_cl, penalty="l2", grad_scale=1.0):
     """(Grad3d(penalty) as a device scalar, grad_scale * d loss / d flow) of a CHANNELS-LAST flow (B,D,H,W,3), gradient in the
     same layout -- no autograd node, no planar copy of the flow.  reference: losses.py:6-31, train.py:128"""
-    _chk(flow_cl)
-    if flow_cl.dim() != 5 or flow_cl.shape[-1] != 3:
-        raise RuntimeError("Grad3d: expects a channels-last (B,D,H,W,3) flow")
-    if penalty not in ("l1", "l2"):
-        raise RuntimeError(f"Grad3d: unknown penalty {penalty!r}")
-    B, D, H, W, _ = flow_cl.shape
-    loss = torch.empty(1, dtype=torch.float32, device=flow_cl.device)
-    df = torch.empty_like(flow_cl)
-    L = _L()
-    nb = L.modet_grad3d_ws_bytes(B, D, H, W)
-    ws = _ws(nb, flow_cl)
-    with _Guard(flow_cl, "grad3d_fwd_bwd", 20.0 * flow_cl.numel(), 8.0 * flow_cl.numel()):
-        _call(L.modet_grad3d_fwd_bwd_cl, _p(flow_cl), _p(loss), _p(df), _p(ws), nb, B, D, H, W, 1 if penalty == "l1" else 2,
-              float(grad_scale), _stream())
+    dims = _grad3d_args(flow_cl, penalty, True)
+    loss, df = _grad3d_launch(flow_cl, penalty, dims, True, True, grad_scale)
     return loss.reshape(()), df
 
 

@@ -19,7 +19,7 @@ import torch
 
 from . import data, utils
 from .engine import Trainer, poly_lr
-from .losses import SSIM3D, DisplacementRegularizer, Grad3DiTV, MIND_loss, MutualInformation, localMutualInformation
+from .losses import REG_TERMS, SIM_TERMS
 from .models import ModeT
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
@@ -88,11 +88,11 @@ def make_parser():
                     help="multi-GPU: all-reduce the gradients in three buckets beside the backward (three hipGraph segments)")
     ap.add_argument("--host-loader", action="store_true",
                     help="read the .pkl pair from the host every iteration instead of caching all subjects in HBM")
-    ap.add_argument("--sim", choices=("ncc", "mind", "mi", "lmi", "ssim"), default="ncc",
+    ap.add_argument("--sim", choices=tuple(SIM_TERMS), default="ncc",
                     help="similarity term: NCC_vxm (mono-modal, the reference's train.py), or for multi-modal pairs the MIND-SSC distance "
                          "MIND_loss, MutualInformation (mi) or localMutualInformation over 5^3 patches (lmi); or 1 - SSIM under an 11^3 Gaussian "
                          "window, SSIM3D (ssim)")
-    ap.add_argument("--reg", choices=("grad3d", "itv", "gradient-l2", "gradient-l1", "bending"), default="grad3d",
+    ap.add_argument("--reg", choices=tuple(REG_TERMS), default="grad3d",
                     help="flow regulariser: Grad3d('l2') (the reference's train.py), the isotropic total variation Grad3DiTV (itv), or "
                          "DisplacementRegularizer's central-difference gradient norms (gradient-l2, gradient-l1) or bending energy "
                          "(bending), the usual partner of mi and mind")
@@ -144,10 +144,7 @@ def main(argv=None):
             print(ck)
     trainer = Trainer(model, lr=args.lr, max_epoch=args.max_epoch, weights=weights,   # Adam(amsgrad) + NCC + Grad3d('l2')
                       overlap_allreduce=args.overlap_allreduce,
-                      sim={"ncc": None, "mind": MIND_loss(), "mi": MutualInformation(), "lmi": localMutualInformation(),
-                           "ssim": SSIM3D()}[args.sim],
-                      reg={"grad3d": None, "itv": Grad3DiTV(), "gradient-l2": DisplacementRegularizer("gradient-l2"),
-                           "gradient-l1": DisplacementRegularizer("gradient-l1"), "bending": DisplacementRegularizer("bending")}[args.reg])
+                      sim=SIM_TERMS[args.sim](), reg=REG_TERMS[args.reg]())
     if resume is not None and not args.no_restore_optimizer and isinstance(resume.get("optimizer"), dict) \
             and "state" in resume["optimizer"]:
         # the reference saves optimizer.state_dict() but never loads it back (train.py:80-85): a resumed run restarts

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.guard_family import check_family_table
 from tests import guard, mi_oracle
 from tests.util import gold
 
@@ -57,22 +58,9 @@ def test_goldens_hold_the_cases_the_gpu_tests_rely_on():
 
 
 def test_mi_header_table_and_exports_agree():
-    """every name include/modet_hip_mi.h declares has a signature in _lib.MI_SIGNATURES and is exported by the library, and the
-    table holds nothing else; the two older tables and headers stay as they are"""
-    from smilecode_amd import _lib, build
-    build.build(verbose=False)
-    lib = _lib.load()
-    declared = _lib.header_symbols(_lib.MI_HEADER_PATH)
-    assert set(declared) == {"modet_mi_ws_bytes", "modet_mi_fwd_bwd", "modet_lmi_fwd_bwd"}
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/modet_hip_mi.h but not exported"
-        assert name in _lib.MI_SIGNATURES, f"{name} has no ctypes signature"
-        fn = getattr(lib, name)
-        assert fn.restype is _lib.MI_SIGNATURES[name][0] and list(fn.argtypes) == _lib.MI_SIGNATURES[name][1]
-    assert set(_lib.MI_SIGNATURES) == set(declared)
-    assert not set(_lib.MI_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.LOSS_SIGNATURES))
-    assert not set(declared) & (set(_lib.header_symbols()) | set(_lib.header_symbols(_lib.LOSS_HEADER_PATH)))
-    assert sorted(n for n in _lib.MI_SIGNATURES if guard.is_launching(n)) == ["modet_lmi_fwd_bwd", "modet_mi_fwd_bwd"]
+    """every name include/modet_hip_mi.h declares has a signature in _lib.FAMILIES["mi"] and is exported by the library, the
+    table holds nothing else and shares no name with another family (tests/guard_family.py)"""
+    check_family_table("mi", {"modet_mi_ws_bytes", "modet_mi_fwd_bwd", "modet_lmi_fwd_bwd"}, ["modet_lmi_fwd_bwd", "modet_mi_fwd_bwd"])
 
 
 def test_workspace_holds_nothing_per_voxel_and_bin():
@@ -150,7 +138,7 @@ def test_loss_classes_refuse_what_they_cannot_compute():
 def test_ops_check_parameters_before_the_launch(monkeypatch):
     """with tensors that claim to be on the GPU the parameter checks still fire first: the library is never reached"""
     from smilecode_amd import _lib, ops
-    monkeypatch.setattr(_lib, "_lib", guard.LibProxy(_lib.load(), signatures=_lib.MI_SIGNATURES, segments=lambda: [], refuse=True))
+    monkeypatch.setattr(_lib, "_lib", guard.LibProxy(_lib.load(), signatures=_lib.FAMILIES["mi"][1], segments=lambda: [], refuse=True))
     monkeypatch.setattr(ops, "_chk", lambda *ts: None)
     v = torch.zeros(1, 1, 4, 5, 6)
     for fn in (ops.mi_loss, ops.lmi_loss, ops.mi_value_and_grad, ops.lmi_value_and_grad):

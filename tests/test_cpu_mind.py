@@ -4,7 +4,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests import guard, mind_oracle
+from tests.guard_family import check_family_table
+from tests import mind_oracle
 from tests.util import gold
 
 CASES = ("pair16", "pair12x20x28", "noise2x10x12x14", "tiny3x4x5")
@@ -46,23 +47,10 @@ def test_aten_composition_equals_the_gather_form_in_fp64():
 
 
 def test_loss_header_table_and_exports_agree():
-    """every name include/modet_hip_losses.h declares has a signature in _lib.LOSS_SIGNATURES and is exported by the library, and
-    the table holds nothing else; the core table and header stay as they are (the family is attached beside them)"""
-    from smilecode_amd import _lib, build
-    build.build(verbose=False)
-    lib = _lib.load()
-    declared = _lib.header_symbols(_lib.LOSS_HEADER_PATH)
-    assert {"modet_mind_ws_bytes", "modet_mind_descriptor", "modet_mind_fwd_bwd"} <= set(declared)
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/modet_hip_losses.h but not exported"
-        assert name in _lib.LOSS_SIGNATURES, f"{name} has no ctypes signature"
-        fn = getattr(lib, name)
-        assert fn.restype is _lib.LOSS_SIGNATURES[name][0] and list(fn.argtypes) == _lib.LOSS_SIGNATURES[name][1]
-    assert set(_lib.LOSS_SIGNATURES) == set(declared)
-    assert not set(_lib.LOSS_SIGNATURES) & set(_lib.SIGNATURES)
-    assert not set(declared) & set(_lib.header_symbols())
-    launching = sorted(n for n in _lib.LOSS_SIGNATURES if guard.is_launching(n))
-    assert launching == ["modet_mind_descriptor", "modet_mind_fwd_bwd"]
+    """every name include/modet_hip_losses.h declares has a signature in _lib.FAMILIES["mind"] and is exported by the library, and
+    the table holds nothing else and shares no name with another family (tests/guard_family.py)"""
+    lib = check_family_table("mind", {"modet_mind_ws_bytes", "modet_mind_descriptor", "modet_mind_fwd_bwd"},
+                             ["modet_mind_descriptor", "modet_mind_fwd_bwd"])
     # host-side answers (no device needed): 12 volumes per image + partials; bad arguments give 0
     n = 160 * 192 * 160
     assert lib.modet_mind_ws_bytes(1, 160, 192, 160, 1) >= 12 * n * 4

@@ -2,12 +2,12 @@
 results, the header of the family against its ctypes table and the library's exports, the workspace size, the refusals, the
 argument checks, the trainer's ``reg`` argument and train.py's flags."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from tests.guard_family import check_family_table, check_header_is_c99
 from tests import guard, reg_oracle
 from tests.util import gold
 
@@ -64,29 +64,11 @@ def test_goldens_hold_the_cases_the_gpu_tests_rely_on():
 
 
 def test_reg_header_table_and_exports_agree():
-    """every name include/modet_hip_reg.h declares has a signature in _lib.REG_SIGNATURES and is exported by the library, and the
-    table holds nothing else; the four older tables and headers stay as they are"""
-    from smilecode_amd import _lib, build
-    build.build(verbose=False)
-    lib = _lib.load()
-    declared = _lib.header_symbols(_lib.REG_HEADER_PATH)
-    assert set(declared) == {"modet_reg_ws_bytes", "modet_reg_fwd_bwd"}
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/modet_hip_reg.h but not exported"
-        assert name in _lib.REG_SIGNATURES, f"{name} has no ctypes signature"
-        fn = getattr(lib, name)
-        assert fn.restype is _lib.REG_SIGNATURES[name][0] and list(fn.argtypes) == _lib.REG_SIGNATURES[name][1]
-    assert set(_lib.REG_SIGNATURES) == set(declared)
-    tables = [_lib.SIGNATURES, _lib.LOSS_SIGNATURES, _lib.MI_SIGNATURES, _lib.SSIM_SIGNATURES, _lib.REG_SIGNATURES]
-    for i, a in enumerate(tables):
-        for b in tables[i + 1:]:
-            assert not set(a) & set(b)
-    older = set()
-    for path in (None, _lib.LOSS_HEADER_PATH, _lib.MI_HEADER_PATH, _lib.SSIM_HEADER_PATH):
-        older |= set(_lib.header_symbols(path))
-    assert not set(declared) & older
-    assert sorted(n for n in _lib.REG_SIGNATURES if guard.is_launching(n)) == ["modet_reg_fwd_bwd"]
-    txt = open(_lib.REG_HEADER_PATH).read()
+    """every name include/modet_hip_reg.h declares has a signature in _lib.FAMILIES["reg"] and is exported by the library, the
+    table holds nothing else and shares no name with another family (tests/guard_family.py)"""
+    check_family_table("reg", {"modet_reg_ws_bytes", "modet_reg_fwd_bwd"}, ["modet_reg_fwd_bwd"])
+    from smilecode_amd import _lib
+    txt = open(_lib.FAMILIES["reg"][0]).read()
     for name, value in KIND_ID.items():
         assert "MODET_REG_%s = %d" % (name.upper().replace("-", "_"), value) in txt
     from smilecode_amd import ops
@@ -94,12 +76,7 @@ def test_reg_header_table_and_exports_agree():
 
 
 def test_header_parses_as_c99(tmp_path):
-    from smilecode_amd import _lib
-    src = tmp_path / "use_reg.c"
-    src.write_text('#include "modet_hip_reg.h"\nint main(void) { return modet_reg_ws_bytes(MODET_REG_BENDING, 0, 0, 0, 0, 0) != 0; }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(_lib.REG_HEADER_PATH), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_c99("reg", tmp_path, "return modet_reg_ws_bytes(MODET_REG_BENDING, 0, 0, 0, 0, 0) != 0;")
 
 
 def test_workspace_holds_partials_only_and_is_a_function_of_kind_and_shape():
@@ -195,7 +172,7 @@ class _Fake:
 def test_ops_check_arguments_before_the_launch(monkeypatch):
     """with tensors that claim to be on the GPU the argument checks still fire first: the library is never reached"""
     from smilecode_amd import _lib, ops
-    px = guard.LibProxy(_lib.load(), signatures=_lib.REG_SIGNATURES, segments=lambda: [], refuse=True)
+    px = guard.LibProxy(_lib.load(), signatures=_lib.FAMILIES["reg"][1], segments=lambda: [], refuse=True)
     monkeypatch.setattr(_lib, "_lib", px)
     with pytest.raises(RuntimeError, match="float32"):         # (the dtype is looked at before the shape is)
         ops._reg_args("reg_loss", _Fake(torch.float64), "bending", False)

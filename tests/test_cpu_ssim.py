@@ -1,12 +1,11 @@
 """The SSIM3D loss without a GPU: the torch restatement against the reference's recorded results, the header of the family
 against its ctypes table and the library's exports, the workspace size, the refusals and the argument checks."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from tests.guard_family import check_family_table, check_header_is_c99
 from tests import guard, ssim_oracle
 from tests.util import gold
 
@@ -48,33 +47,13 @@ def test_goldens_hold_the_cases_the_gpu_tests_rely_on():
 
 
 def test_ssim_header_table_and_exports_agree():
-    """every name include/modet_hip_ssim.h declares has a signature in _lib.SSIM_SIGNATURES and is exported by the library, and
-    the table holds nothing else; the three older tables and headers stay as they are"""
-    from smilecode_amd import _lib, build
-    build.build(verbose=False)
-    lib = _lib.load()
-    declared = _lib.header_symbols(_lib.SSIM_HEADER_PATH)
-    assert set(declared) == {"modet_ssim_ws_bytes", "modet_ssim_fwd_bwd"}
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/modet_hip_ssim.h but not exported"
-        assert name in _lib.SSIM_SIGNATURES, f"{name} has no ctypes signature"
-        fn = getattr(lib, name)
-        assert fn.restype is _lib.SSIM_SIGNATURES[name][0] and list(fn.argtypes) == _lib.SSIM_SIGNATURES[name][1]
-    assert set(_lib.SSIM_SIGNATURES) == set(declared)
-    others = set(_lib.SIGNATURES) | set(_lib.LOSS_SIGNATURES) | set(_lib.MI_SIGNATURES)
-    assert not set(_lib.SSIM_SIGNATURES) & others
-    assert not set(declared) & (set(_lib.header_symbols()) | set(_lib.header_symbols(_lib.LOSS_HEADER_PATH))
-                                | set(_lib.header_symbols(_lib.MI_HEADER_PATH)))
-    assert sorted(n for n in _lib.SSIM_SIGNATURES if guard.is_launching(n)) == ["modet_ssim_fwd_bwd"]
+    """every name include/modet_hip_ssim.h declares has a signature in _lib.FAMILIES["ssim"] and is exported by the library,
+    the table holds nothing else and shares no name with another family (tests/guard_family.py)"""
+    check_family_table("ssim", {"modet_ssim_ws_bytes", "modet_ssim_fwd_bwd"}, ["modet_ssim_fwd_bwd"])
 
 
 def test_header_parses_as_c99(tmp_path):
-    from smilecode_amd import _lib
-    src = tmp_path / "use_ssim.c"
-    src.write_text('#include "modet_hip_ssim.h"\nint main(void) { return modet_ssim_ws_bytes(0, 0, 0, 0, 0) != 0; }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(_lib.SSIM_HEADER_PATH), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_c99("ssim", tmp_path, "return modet_ssim_ws_bytes(0, 0, 0, 0, 0) != 0;")
 
 
 def test_workspace_is_at_most_five_volumes_and_a_function_of_shape_and_window():
@@ -145,7 +124,7 @@ def test_loss_class_refuses_what_it_cannot_compute():
 def test_ops_check_arguments_before_the_launch(monkeypatch):
     """with tensors that claim to be on the GPU the argument checks still fire first: the library is never reached"""
     from smilecode_amd import _lib, losses, ops
-    px = guard.LibProxy(_lib.load(), signatures=_lib.SSIM_SIGNATURES, segments=lambda: [], refuse=True)
+    px = guard.LibProxy(_lib.load(), signatures=_lib.FAMILIES["ssim"][1], segments=lambda: [], refuse=True)
     monkeypatch.setattr(_lib, "_lib", px)
     v = torch.zeros(1, 1, 4, 5, 6)
     with pytest.raises(RuntimeError, match="float32"):         # (the dtype is looked at before the shape is)

@@ -2,13 +2,12 @@
 parity case, the sixth header / table / export agreement, host-side answers of modet_vecint_ws_bytes, the argument checks of
 ops.vecint in front of the library, and the public signatures (VecInt, ModeT(diff=...), the train and infer parsers)."""
 import inspect
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from tests.guard_family import check_family_table, check_header_is_c99
 from tests import guard
 from tests import vecint_oracle as vo
 from tests.util import gold
@@ -52,41 +51,16 @@ def test_case_bounds_split_the_steps_as_the_tests_say():
 
 
 def test_vecint_header_table_and_exports_agree():
-    """every name include/modet_hip_vecint.h declares has a signature in _lib.VECINT_SIGNATURES and is exported by the library,
-    and the table holds nothing else; the five older tables and headers stay as they are"""
+    """every name include/modet_hip_vecint.h declares has a signature in _lib.FAMILIES["vecint"] and is exported by the library,
+    the table holds nothing else and shares no name with another family (tests/guard_family.py)"""
+    check_family_table("vecint", {"modet_vecint_fwd", "modet_vecint_ws_bytes", "modet_vecint_bwd"}, ["modet_vecint_bwd", "modet_vecint_fwd"])
     from smilecode_amd import _lib, build, ops
-    build.build(verbose=False)
-    lib = _lib.load()
-    declared = _lib.header_symbols(_lib.VECINT_HEADER_PATH)
-    assert set(declared) == {"modet_vecint_fwd", "modet_vecint_ws_bytes", "modet_vecint_bwd"}
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/modet_hip_vecint.h but not exported"
-        assert name in _lib.VECINT_SIGNATURES, f"{name} has no ctypes signature"
-        fn = getattr(lib, name)
-        assert fn.restype is _lib.VECINT_SIGNATURES[name][0] and list(fn.argtypes) == _lib.VECINT_SIGNATURES[name][1]
-    assert set(_lib.VECINT_SIGNATURES) == set(declared)
-    tables = [_lib.SIGNATURES, _lib.LOSS_SIGNATURES, _lib.MI_SIGNATURES, _lib.SSIM_SIGNATURES, _lib.REG_SIGNATURES,
-              _lib.VECINT_SIGNATURES]
-    for i, a in enumerate(tables):
-        for b in tables[i + 1:]:
-            assert not set(a) & set(b)
-    older = set()
-    for path in (None, _lib.LOSS_HEADER_PATH, _lib.MI_HEADER_PATH, _lib.SSIM_HEADER_PATH, _lib.REG_HEADER_PATH):
-        older |= set(_lib.header_symbols(path))
-    assert not set(declared) & older
-    assert sorted(n for n in _lib.VECINT_SIGNATURES if guard.is_launching(n)) == ["modet_vecint_bwd", "modet_vecint_fwd"]
-    assert "MODET_VECINT_MAX_STEPS = %d" % ops.VECINT_MAX_STEPS in open(_lib.VECINT_HEADER_PATH).read()
+    assert "MODET_VECINT_MAX_STEPS = %d" % ops.VECINT_MAX_STEPS in open(_lib.FAMILIES["vecint"][0]).read()
     assert "vecint.hip" in build.SOURCES
 
 
 def test_header_parses_as_c99(tmp_path):
-    from smilecode_amd import _lib
-    src = tmp_path / "use_vecint.c"
-    src.write_text('#include "modet_hip_vecint.h"\nint main(void) { return modet_vecint_ws_bytes(0, 0, 0, 0, MODET_VECINT_MAX_STEPS, '
-                   '0.f) != 0; }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(_lib.VECINT_HEADER_PATH), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_c99("vecint", tmp_path, "return modet_vecint_ws_bytes(0, 0, 0, 0, MODET_VECINT_MAX_STEPS, 0.f) != 0;")
 
 
 def test_workspace_size_answers_on_the_host():
@@ -128,7 +102,7 @@ class _Fake:
 def test_ops_check_arguments_before_the_launch(monkeypatch):
     """every refusal of ops.vecint fires before the library is reached"""
     from smilecode_amd import _lib, ops
-    px = guard.LibProxy(_lib.load(), signatures=_lib.VECINT_SIGNATURES, segments=lambda: [], refuse=True)
+    px = guard.LibProxy(_lib.load(), signatures=_lib.FAMILIES["vecint"][1], segments=lambda: [], refuse=True)
     monkeypatch.setattr(_lib, "_lib", px)
     with pytest.raises(RuntimeError, match="float32"):
         ops.vecint(_Fake(torch.float64))

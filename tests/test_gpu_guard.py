@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from tests import guard
+from tests.guard_family import Maker
 from tests.util import note_many
 
 pytestmark = pytest.mark.gpu
@@ -44,28 +45,6 @@ def G(seed):
 
 def R(gen, *shape, s=1.0):
     return torch.randn(*shape, generator=gen) * s
-
-
-class Maker:
-    """puts a case's tensors on the GPU: plain (mode None), or between bands of 0xFF / 0x00 bytes"""
-
-    def __init__(self, mode):
-        self.mode = mode
-
-    def __call__(self, t):
-        return t.cuda() if self.mode is None else guard.guarded(t.cuda(), canary=self.mode)
-
-    def empty(self, shape, dtype=torch.float32):
-        """an output buffer (poisoned when guarded)"""
-        if self.mode is None:
-            return torch.empty(shape, dtype=dtype, device="cuda")
-        return guard.guarded_empty(shape, dtype, "cuda", canary=self.mode)
-
-    def ws(self, nbytes):
-        """a workspace of exactly nbytes (guarded: poisoned, and every byte behind it is band; plain: rounded up to 4)"""
-        if self.mode is None:
-            return torch.empty(-(-int(nbytes) // 4) * 4, dtype=torch.uint8, device="cuda")
-        return guard.guarded_bytes(nbytes, "cuda", canary=self.mode)
 
 
 def _run(case, mode, px, section):

@@ -1,90 +1,19 @@
 """-m gpu: WHERE the MIND kernels read and write -- tests/test_gpu_guard.py's four assertions over the loss family's own table
-(_lib.LOSS_SIGNATURES, include/modet_hip_losses.h).  Every caller-supplied tensor sits between guard bands (tests/guard.py),
+(_lib.FAMILIES["mind"], include/modet_hip_losses.h).  Every caller-supplied tensor sits between guard bands (tests/guard.py),
 workspaces are exactly modet_mind_ws_bytes(...) bytes, outputs and workspaces are poisoned, and the library is reached through a
 recording proxy over the new table.  Per case: no band is damaged, every result is finite, the results equal an unguarded run
 bit for bit, and a second guarded run with 0x00 instead of 0xFF bands and poison gives the same bits.  Shapes have odd
 dimensions, one smaller than the stencil's reach.  The coverage condition of the core table is restated over the new one."""
-import contextlib
-
 import pytest
 import torch
 
 from tests import guard
+from tests.guard_family import Harness, stream
 
 pytestmark = pytest.mark.gpu
 
-SEEN = []        # the proxies' (entry point, [class of each pointer argument]) records of the 0xFF runs
-RAN = set()
-
-
-@pytest.fixture
-def px(monkeypatch):
-    from smilecode_amd import _lib
-    p = guard.LibProxy(_lib.load(), signatures=_lib.LOSS_SIGNATURES)
-    monkeypatch.setattr(_lib, "_lib", p)
-    guard.release()
-    yield p
-    guard.release()
-    torch.cuda.empty_cache()
-
-
-class Maker:
-    """puts a case's tensors on the GPU: plain (mode None), or between bands of 0xFF / 0x00 bytes"""
-
-    def __init__(self, mode):
-        self.mode = mode
-
-    def __call__(self, t):
-        return t.cuda() if self.mode is None else guard.guarded(t.cuda(), canary=self.mode)
-
-    def empty(self, shape, dtype=torch.float32):
-        if self.mode is None:
-            return torch.empty(shape, dtype=dtype, device="cuda")
-        return guard.guarded_empty(shape, dtype, "cuda", canary=self.mode)
-
-    def ws(self, nbytes):
-        if self.mode is None:
-            return torch.empty(-(-int(nbytes) // 4) * 4, dtype=torch.uint8, device="cuda")
-        return guard.guarded_bytes(nbytes, "cuda", canary=self.mode)
-
-
-def _run(case, mode, px):
-    g, ctx = Maker(mode), (contextlib.nullcontext() if mode is None else guard.GuardedAlloc(canary=mode))
-    n0, outs = len(px.records), {}
-    with ctx:
-        named = case(g)
-        torch.cuda.synchronize()
-        if mode is not None:
-            bands = guard.check()
-            assert not bands, guard.describe(bands)
-        for k, v in named.items():
-            outs[k] = v.detach().clone()
-    if mode == 0xFF:
-        SEEN.extend(px.records[n0:])
-    del px.records[n0:]
-    guard.release()
-    return outs
-
-
-def _same(a, b, what, tag):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert a[k].shape == b[k].shape and torch.equal(a[k], b[k]), "%s: %s differs (%s): max |diff| %.3e" % (
-            tag, k, what, float((a[k].double() - b[k].double()).abs().max()))
-
-
-def run_guarded(case, px, tag):
-    plain = _run(case, None, px)
-    first = _run(case, 0xFF, px)
-    for k, v in first.items():
-        assert bool(torch.isfinite(v).all()), "%s: %s is not finite in the guarded run (a read of a band or of poison)" % (tag, k)
-    _same(first, plain, "guarded vs unguarded", tag)
-    second = _run(case, 0x00, px)
-    _same(second, first, "0x00 vs 0xFF bands and poison", tag)
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
+H = Harness("mind")
+px = H.fixture()
 
 
 def abi_case(shape, B):
@@ -97,13 +26,13 @@ def abi_case(shape, B):
         n1, n2 = L.modet_mind_ws_bytes(B, D, H, W, 1), L.modet_mind_ws_bytes(B, D, H, W, 2)
         assert 0 < n1 < n2
         desc, ws = g.empty((B, 12, D, H, W)), g.ws(n1)
-        _lib.check(L.modet_mind_descriptor(a.data_ptr(), desc.data_ptr(), ws.data_ptr(), n1, B, D, H, W, 2, 2, _st()), "descriptor")
+        _lib.check(L.modet_mind_descriptor(a.data_ptr(), desc.data_ptr(), ws.data_ptr(), n1, B, D, H, W, 2, 2, stream()), "descriptor")
         loss, d_b, ws2 = g.empty(1), g.empty(b.shape), g.ws(n2)
         _lib.check(L.modet_mind_fwd_bwd(a.data_ptr(), b.data_ptr(), loss.data_ptr(), d_b.data_ptr(), ws2.data_ptr(), n2, B, D, H, W,
-                                        2, 2, 0.37, _st()), "fwd_bwd")
+                                        2, 2, 0.37, stream()), "fwd_bwd")
         loss0, ws3 = g.empty(1), g.ws(n2)
         _lib.check(L.modet_mind_fwd_bwd(a.data_ptr(), b.data_ptr(), loss0.data_ptr(), None, ws3.data_ptr(), n2, B, D, H, W,
-                                        2, 2, 1.0, _st()), "fwd")
+                                        2, 2, 1.0, stream()), "fwd")
         return dict(desc=desc, loss=loss, d_b=d_b, loss_nograd=loss0)
     return case
 
@@ -136,8 +65,8 @@ CASES = {
 
 @pytest.mark.parametrize("tag", sorted(CASES))
 def test_mind_between_guard_bands(px, tag):
-    run_guarded(CASES[tag], px, tag)
-    RAN.add(tag)
+    H.run_guarded(CASES[tag], px, tag)
+    H.ran.add(tag)
 
 
 def test_entry_points_refuse_before_any_launch(px):
@@ -157,19 +86,7 @@ def test_entry_points_refuse_before_any_launch(px):
 
 def test_every_launching_mind_entry_point_ran_between_guard_bands(px):
     """the coverage condition of tests/test_gpu_guard.py over the loss family's table: every launching name of
-    _lib.LOSS_SIGNATURES was called at least once with every device pointer inside a guarded buffer, and no case handed the library
+    _lib.FAMILIES["mind"] was called at least once with every device pointer inside a guarded buffer, and no case handed the library
     a device pointer outside one.  Cases deselected from this session are run here, guarded once."""
-    from smilecode_amd import _lib
-    for tag in sorted(CASES):
-        if tag not in RAN:
-            _run(CASES[tag], 0xFF, px)
-    need = sorted(n for n in _lib.LOSS_SIGNATURES if guard.is_launching(n))
-    assert need == ["modet_mind_descriptor", "modet_mind_fwd_bwd"]
-    clean = {n for n, cs in SEEN if "torch" not in cs}
-    missing = [n for n in need if n not in clean]
-    loose = sorted({n for n, cs in SEEN if "torch" in cs})
-    assert not missing, "entry points never called with all device pointers guarded: " + ", ".join(missing)
-    assert not loose, "cases handed the library pointers outside every guarded buffer: " + ", ".join(loose)
-    # both forms of the loss call were seen: with a gradient buffer and with NULL
-    d_b = {cs[3] for n, cs in SEEN if n == "modet_mind_fwd_bwd"}          # pointer arguments: a, b, loss, d_b, ws, stream
-    assert d_b == {"guarded", "null"}, d_b
+    # both forms of the loss call were seen: with a gradient buffer and with NULL (pointer arguments: a, b, loss, d_b, ws, stream)
+    H.check_coverage(px, CASES, {"modet_mind_descriptor": ((), ()), "modet_mind_fwd_bwd": ((3,), ())})

@@ -1,92 +1,21 @@
 """-m gpu: WHERE the flow-regulariser kernels read and write -- tests/test_gpu_ssim_guard.py's assertions over the family's own table
-(_lib.REG_SIGNATURES, include/modet_hip_reg.h).  Every caller-supplied tensor sits between guard bands (tests/guard.py),
+(_lib.FAMILIES["reg"], include/modet_hip_reg.h).  Every caller-supplied tensor sits between guard bands (tests/guard.py),
 workspaces are exactly modet_reg_ws_bytes(...) bytes, outputs and workspaces are poisoned, and the library is reached through a
 recording proxy over the new table.  Per case: no band is damaged, every result is finite, the results equal an unguarded run
 bit for bit, and a second guarded run with 0x00 instead of 0xFF bands and poison gives the same bits.  The stencils reach 1, 2 and
 4 voxels along every axis, so the shapes are each kind's minimum (where every neighbour but the voxel itself is outside), odd
 sizes with every voxel in bending's shell (5^3, 7 x 9 x 37) and one with interior voxels and rows longer than a wave (9 x 27 x 67),
 in both layouts, with the gradient present and absent."""
-import contextlib
-
 import pytest
 import torch
 
 from tests import guard
+from tests.guard_family import Harness, stream
 
 pytestmark = pytest.mark.gpu
 
-SEEN = []        # the proxies' (entry point, [class of each pointer argument]) records of the 0xFF runs
-RAN = set()
-
-
-@pytest.fixture
-def px(monkeypatch):
-    from smilecode_amd import _lib
-    p = guard.LibProxy(_lib.load(), signatures=_lib.REG_SIGNATURES)
-    monkeypatch.setattr(_lib, "_lib", p)
-    guard.release()
-    yield p
-    guard.release()
-    torch.cuda.empty_cache()
-
-
-class Maker:
-    """puts a case's tensors on the GPU: plain (mode None), or between bands of 0xFF / 0x00 bytes"""
-
-    def __init__(self, mode):
-        self.mode = mode
-
-    def __call__(self, t):
-        return t.cuda() if self.mode is None else guard.guarded(t.cuda(), canary=self.mode)
-
-    def empty(self, shape, dtype=torch.float32):
-        if self.mode is None:
-            return torch.empty(shape, dtype=dtype, device="cuda")
-        return guard.guarded_empty(shape, dtype, "cuda", canary=self.mode)
-
-    def ws(self, nbytes):
-        if self.mode is None:
-            return torch.empty(-(-int(nbytes) // 4) * 4, dtype=torch.uint8, device="cuda")
-        return guard.guarded_bytes(nbytes, "cuda", canary=self.mode)
-
-
-def _run(case, mode, px):
-    g, ctx = Maker(mode), (contextlib.nullcontext() if mode is None else guard.GuardedAlloc(canary=mode))
-    n0, outs = len(px.records), {}
-    with ctx:
-        named = case(g)
-        torch.cuda.synchronize()
-        if mode is not None:
-            bands = guard.check()
-            assert not bands, guard.describe(bands)
-        for k, v in named.items():
-            outs[k] = v.detach().clone()
-    if mode == 0xFF:
-        SEEN.extend(px.records[n0:])
-    del px.records[n0:]
-    guard.release()
-    return outs
-
-
-def _same(a, b, what, tag):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert a[k].shape == b[k].shape and torch.equal(a[k], b[k]), "%s: %s differs (%s): max |diff| %.3e" % (
-            tag, k, what, float((a[k].double() - b[k].double()).abs().max()))
-
-
-def run_guarded(case, px, tag):
-    plain = _run(case, None, px)
-    first = _run(case, 0xFF, px)
-    for k, v in first.items():
-        assert bool(torch.isfinite(v).all()), "%s: %s is not finite in the guarded run (a read of a band or of poison)" % (tag, k)
-    _same(first, plain, "guarded vs unguarded", tag)
-    second = _run(case, 0x00, px)
-    _same(second, first, "0x00 vs 0xFF bands and poison", tag)
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
+H = Harness("reg")
+px = H.fixture()
 
 
 def abi_case(kind, shape, B, C=3):
@@ -106,7 +35,7 @@ def abi_case(kind, shape, B, C=3):
                 loss, ws = g.empty(1), g.ws(nb)
                 d_f = g.empty(f.shape) if want else None
                 rc = L.modet_reg_fwd_bwd(f.data_ptr(), loss.data_ptr(), None if d_f is None else d_f.data_ptr(), ws.data_ptr(), nb, kid,
-                                         B, C, D, H, W, cl, 0.37, _st())
+                                         B, C, D, H, W, cl, 0.37, stream())
                 _lib.check(rc, "reg %s" % kind)
                 k = "cl%d.%d." % (cl, want)
                 out[k + "loss"] = loss
@@ -150,8 +79,8 @@ CASES["ops[5x6x7]"] = ops_case((5, 6, 7), 1)
 
 @pytest.mark.parametrize("tag", sorted(CASES))
 def test_reg_between_guard_bands(px, tag):
-    run_guarded(CASES[tag], px, tag)
-    RAN.add(tag)
+    H.run_guarded(CASES[tag], px, tag)
+    H.ran.add(tag)
 
 
 def test_entry_points_refuse_before_any_launch(px):
@@ -179,21 +108,8 @@ def test_entry_points_refuse_before_any_launch(px):
 
 
 def test_every_launching_reg_entry_point_ran_between_guard_bands(px):
-    """the coverage condition of tests/test_gpu_guard.py over the family's table: every launching name of _lib.REG_SIGNATURES was
+    """the coverage condition of tests/test_gpu_guard.py over the family's table: every launching name of _lib.FAMILIES["reg"] was
     called at least once with every device pointer inside a guarded buffer, and no case handed the library a device pointer
     outside one.  Cases deselected from this session are run here, guarded once."""
-    from smilecode_amd import _lib
-    for tag in sorted(CASES):
-        if tag not in RAN:
-            _run(CASES[tag], 0xFF, px)
-    need = sorted(n for n in _lib.REG_SIGNATURES if guard.is_launching(n))
-    assert need == ["modet_reg_fwd_bwd"]
-    clean = {n for n, cs in SEEN if "torch" not in cs}
-    missing = [n for n in need if n not in clean]
-    loose = sorted({n for n, cs in SEEN if "torch" in cs})
-    assert not missing, "entry points never called with all device pointers guarded: " + ", ".join(missing)
-    assert not loose, "cases handed the library pointers outside every guarded buffer: " + ", ".join(loose)
     # the gradient buffer was seen present and absent (pointer arguments: f, loss, d_f, ws, stream)
-    for n in need:
-        assert {cs[2] for m, cs in SEEN if m == n} == {"guarded", "null"}, n
-        assert {cs[i] for m, cs in SEEN if m == n for i in (0, 1, 3)} == {"guarded"}, n
+    H.check_coverage(px, CASES, {"modet_reg_fwd_bwd": ((2,), (0, 1, 3))})

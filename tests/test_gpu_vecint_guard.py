@@ -1,92 +1,21 @@
 """-m gpu: WHERE the velocity-integration kernels read and write -- tests/test_gpu_reg_guard.py's assertions over the family's own
-table (_lib.VECINT_SIGNATURES, include/modet_hip_vecint.h).  Every caller-supplied tensor sits between guard bands
+table (_lib.FAMILIES["vecint"], include/modet_hip_vecint.h).  Every caller-supplied tensor sits between guard bands
 (tests/guard.py), workspaces are exactly modet_vecint_ws_bytes(...) bytes, outputs, step buffers, scratch fields and workspaces
 are poisoned, and the library is reached through a recording proxy over the new table.  Per case: no band is damaged, every
 result is finite, the results equal an unguarded run bit for bit, and a second guarded run with 0x00 instead of 0xFF bands and
 poison gives the same bits.  Samples leave the volume in every case with amp > 1 (by many voxels at amp 12); the shapes have every
 voxel on the border (5 x 6 x 7), a row longer than a wave (4 x 5 x 67) and partial 4 x 4 x 16 tiles along every axis.  Fields with
 entries of 1e30 and a NaN voxel, and a broken bound promise, assert intact bands only."""
-import contextlib
-
 import pytest
 import torch
 
 from tests import guard
+from tests.guard_family import Harness, stream
 
 pytestmark = pytest.mark.gpu
 
-SEEN = []        # the proxies' (entry point, [class of each pointer argument]) records of the 0xFF runs
-RAN = set()
-
-
-@pytest.fixture
-def px(monkeypatch):
-    from smilecode_amd import _lib
-    p = guard.LibProxy(_lib.load(), signatures=_lib.VECINT_SIGNATURES)
-    monkeypatch.setattr(_lib, "_lib", p)
-    guard.release()
-    yield p
-    guard.release()
-    torch.cuda.empty_cache()
-
-
-class Maker:
-    """puts a case's tensors on the GPU: plain (mode None), or between bands of 0xFF / 0x00 bytes"""
-
-    def __init__(self, mode):
-        self.mode = mode
-
-    def __call__(self, t):
-        return t.cuda() if self.mode is None else guard.guarded(t.cuda(), canary=self.mode)
-
-    def empty(self, shape, dtype=torch.float32):
-        if self.mode is None:
-            return torch.empty(shape, dtype=dtype, device="cuda")
-        return guard.guarded_empty(shape, dtype, "cuda", canary=self.mode)
-
-    def ws(self, nbytes):
-        if self.mode is None:
-            return torch.empty(-(-int(nbytes) // 4) * 4, dtype=torch.uint8, device="cuda")
-        return guard.guarded_bytes(nbytes, "cuda", canary=self.mode)
-
-
-def _run(case, mode, px):
-    g, ctx = Maker(mode), (contextlib.nullcontext() if mode is None else guard.GuardedAlloc(canary=mode))
-    n0, outs = len(px.records), {}
-    with ctx:
-        named = case(g)
-        torch.cuda.synchronize()
-        if mode is not None:
-            bands = guard.check()
-            assert not bands, guard.describe(bands)
-        for k, v in named.items():
-            outs[k] = v.detach().clone()
-    if mode == 0xFF:
-        SEEN.extend(px.records[n0:])
-    del px.records[n0:]
-    guard.release()
-    return outs
-
-
-def _same(a, b, what, tag):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert a[k].shape == b[k].shape and torch.equal(a[k], b[k]), "%s: %s differs (%s): max |diff| %.3e" % (
-            tag, k, what, float((a[k].double() - b[k].double()).abs().max()))
-
-
-def run_guarded(case, px, tag):
-    plain = _run(case, None, px)
-    first = _run(case, 0xFF, px)
-    for k, v in first.items():
-        assert bool(torch.isfinite(v).all()), "%s: %s is not finite in the guarded run (a read of a band or of poison)" % (tag, k)
-    _same(first, plain, "guarded vs unguarded", tag)
-    second = _run(case, 0x00, px)
-    _same(second, first, "0x00 vs 0xFF bands and poison", tag)
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
+H = Harness("vecint")
+px = H.fixture()
 
 
 def _field(shape, B, amp, spoil=False):
@@ -117,9 +46,9 @@ def abi_case(shape, B, nsteps, bound, amp, spoil=False):
         scr_b = g.empty(vec.shape) if nsteps >= 2 else None
         ws = g.ws(nb) if nb else None
         p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        _lib.check(L.modet_vecint_fwd(p(vec), p(out_a), p(steps), None, B, D, H, W, nsteps, _st()), "vecint fwd (steps)")
-        _lib.check(L.modet_vecint_fwd(p(vec), p(out_b), None, p(scr_f), B, D, H, W, nsteps, _st()), "vecint fwd (scratch)")
-        _lib.check(L.modet_vecint_bwd(p(vec), p(steps), p(d_out), p(d_vec), p(scr_b), p(ws), nb, B, D, H, W, nsteps, bound, _st()),
+        _lib.check(L.modet_vecint_fwd(p(vec), p(out_a), p(steps), None, B, D, H, W, nsteps, stream()), "vecint fwd (steps)")
+        _lib.check(L.modet_vecint_fwd(p(vec), p(out_b), None, p(scr_f), B, D, H, W, nsteps, stream()), "vecint fwd (scratch)")
+        _lib.check(L.modet_vecint_bwd(p(vec), p(steps), p(d_out), p(d_vec), p(scr_b), p(ws), nb, B, D, H, W, nsteps, bound, stream()),
                    "vecint bwd")
         return {"out": out_a, "out_inference": out_b, "d_vec": d_vec}
     return case
@@ -163,10 +92,10 @@ CASES["ops[broken promise,9x13x35,B2,n7,bound1,amp12]"] = (ops_case((9, 13, 35),
 def test_vecint_between_guard_bands(px, tag):
     case, finite = CASES[tag]
     if finite:
-        run_guarded(case, px, tag)
+        H.run_guarded(case, px, tag)
     else:
-        _run(case, 0xFF, px)          # memory-safe whatever the values are: intact bands (asserted inside), nothing about the results
-    RAN.add(tag)
+        H.run(case, 0xFF, px)          # memory-safe whatever the values are: intact bands (asserted inside), nothing about the results
+    H.ran.add(tag)
 
 
 def test_entry_points_refuse_before_any_launch(px):
@@ -192,7 +121,7 @@ def test_library_refuses_with_error_codes():
     L = _lib.load()
     v = torch.zeros(1, 4, 4, 4, 3, device="cuda")
     o, s, d = torch.full_like(v, 7.0), torch.full_like(v, 7.0), torch.full_like(v, 7.0)
-    P, st = (lambda t: t.data_ptr()), _st()
+    P, st = (lambda t: t.data_ptr()), stream()
     NULL, DIM, WS = -1, -2, -4
     codes = {L.modet_hip_strerror(c).decode(): c for c in (NULL, DIM, WS)}
     assert codes == {"required pointer is NULL": NULL, "invalid or inconsistent dimensions": DIM,
@@ -224,25 +153,11 @@ def test_library_refuses_with_error_codes():
 
 
 def test_every_launching_vecint_entry_point_ran_between_guard_bands(px):
-    """the coverage condition of tests/test_gpu_guard.py over the family's table: every launching name of _lib.VECINT_SIGNATURES
+    """the coverage condition of tests/test_gpu_guard.py over the family's table: every launching name of _lib.FAMILIES["vecint"]
     was called at least once with every device pointer inside a guarded buffer, and no case handed the library a device pointer
     outside one.  Cases deselected from this session are run here, guarded once."""
-    from smilecode_amd import _lib
-    for tag in sorted(CASES):
-        if tag not in RAN:
-            _run(CASES[tag][0], 0xFF, px)
-    need = sorted(n for n in _lib.VECINT_SIGNATURES if guard.is_launching(n))
-    assert need == ["modet_vecint_bwd", "modet_vecint_fwd"]
-    clean = {n for n, cs in SEEN if "torch" not in cs}
-    missing = [n for n in need if n not in clean]
-    loose = sorted({n for n, cs in SEEN if "torch" in cs})
-    assert not missing, "entry points never called with all device pointers guarded: " + ", ".join(missing)
-    assert not loose, "cases handed the library pointers outside every guarded buffer: " + ", ".join(loose)
     # forward (vec, out, steps, scratch, stream): both forms were seen; backward (vec, steps, d_out, d_vec, scratch, ws, stream):
     # with and without a workspace
-    fwd = [cs for m, cs in SEEN if m == "modet_vecint_fwd"]
+    H.check_coverage(px, {tag: c[0] for tag, c in CASES.items()}, {"modet_vecint_fwd": ((), (0, 1)), "modet_vecint_bwd": ((5,), (0, 2, 3))})
+    fwd = [cs for m, cs in H.seen if m == "modet_vecint_fwd"]
     assert {(cs[2], cs[3]) for cs in fwd} >= {("guarded", "null"), ("null", "guarded"), ("null", "null")}
-    assert {cs[i] for cs in fwd for i in (0, 1)} == {"guarded"}
-    bwd = [cs for m, cs in SEEN if m == "modet_vecint_bwd"]
-    assert {cs[5] for cs in bwd} == {"guarded", "null"}
-    assert {cs[i] for cs in bwd for i in (0, 2, 3)} == {"guarded"}

@@ -17,11 +17,11 @@ def main():
         b = torch.rand((B, 1) + shape, device="cuda", generator=g)
         for win in (9, 5):
             for _ in range(3):
-                ops._ncc_launch(a, b, True, win)
+                ops._ncc_once(a, b, True, win)
             ts = []
             for _ in range(20):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); ops._ncc_launch(a, b, True, win); e1.record(); e1.synchronize()
+                e0.record(); ops._ncc_once(a, b, True, win); e1.record(); e1.synchronize()
                 ts.append(e0.elapsed_time(e1))
             ts.sort()
             n = a.numel()
