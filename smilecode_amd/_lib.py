@@ -177,6 +177,10 @@ FAMILIES = {
         "modet_vecint_ws_bytes": (SZ, [I, I, I, I, I, F]),
         "modet_vecint_bwd": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, F, P]),
     }),
+    "surface": (_header("modet_hip_surface.h"), {
+        "modet_surface_ws_bytes": (SZ, [I, I, I, I]),
+        "modet_surface_distances": (I, [P, P, P, P, P, SZ, I, I, I, I, F, P]),
+    }),
 }
 # The names a family's entry had before the registry.  Nothing in this tree uses them; they stay because the previous revision's
 # test files, which every change is also run against, reach the library through them (about 95 test ids).  Views of FAMILIES:

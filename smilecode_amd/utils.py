@@ -91,3 +91,81 @@ def jacobian_determinant_vxm(disp):
     flow_cl = t.permute(1, 2, 3, 0).contiguous()[None]
     _, det = ops.jacdet_nonpos_count(flow_cl, want_det=True)
     return det[0].cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------ surface distances
+# hd_val, hd95_val and assd_val of the reference's Baseline methods/RDN/utils.py:94-116 (medpy's metric.hd / hd95 / assd per label)
+# from ONE device call (ops.surface_distances): nothing but the (nlabels, 5) and (nlabels, 7) result tables comes back.
+_SURFACE_COLUMN = {"hd": 0, "hd95": 1, "assd": 2}
+_SURFACE_EMPTY = ("The first supplied array does not contain any binary object.",
+                  "The second supplied array does not contain any binary object.")
+
+
+def _label_volume(name, a):
+    """one (D,H,W) int16 label map on the GPU from a numpy array or a tensor; leading singleton axes of (1,1,D,H,W) are dropped"""
+    t = torch.as_tensor(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+    if not torch.is_tensor(t):
+        raise RuntimeError(f"surface distances: {name} must be a numpy array or a tensor, got {type(a).__name__}")
+    if t.dim() > 3 and any(int(s) != 1 for s in t.shape[:-3]):
+        raise RuntimeError(f"surface distances: {name} {tuple(t.shape)} holds more than one volume (B > 1 is not supported: "
+                           "score one pair at a time)")
+    if t.dim() < 3:
+        raise RuntimeError(f"surface distances: {name} {tuple(t.shape)} is not a (D,H,W) volume (2-D maps are not supported)")
+    return t.reshape(t.shape[-3:]).to(torch.int16).cuda().contiguous()
+
+
+def _surface_tables(y_pred, y_true, nlabels, voxelspacing=None, connectivity=1):
+    if voxelspacing is not None:
+        raise RuntimeError("surface distances: voxelspacing other than None (unit spacing) is not supported")
+    if connectivity != 1:
+        raise RuntimeError(f"surface distances: connectivity {connectivity!r} is not supported (only 1, the 6 face neighbours)")
+    p, t = _label_volume("y_pred", y_pred), _label_volume("y_true", y_true)
+    metrics, counts = ops.surface_distances(p, t, int(nlabels), 95.0)
+    return metrics.cpu().numpy(), counts.cpu().numpy()
+
+
+def surface_vals(y_pred, y_true, C=None, *, voxelspacing=None, connectivity=1):
+    """{"hd": [...], "hd95": [...], "assd": [...]}: the three lists of hd_val, hd95_val and assd_val from one device call.  Each
+    is the reference's: one value per label 1..C with their mean appended; C defaults to the number of distinct values of y_true
+    (np.unique(y_true).shape[0], as there).  A label in 1..C that is empty in y_pred (the first array medpy is handed) or y_true
+    (the second) raises RuntimeError with medpy's message."""
+    if not C:
+        yt = torch.as_tensor(np.ascontiguousarray(y_true)) if isinstance(y_true, np.ndarray) else y_true
+        C = int(torch.unique(yt).numel())
+    metrics, counts = _surface_tables(y_pred, y_true, C, voxelspacing, connectivity)
+    for i in range(C):
+        for side in (0, 1):
+            if counts[i, side] == 0:
+                raise RuntimeError(_SURFACE_EMPTY[side])
+    out = {}
+    for name, col in _SURFACE_COLUMN.items():
+        total = [np.float64(v) for v in metrics[:, col]]
+        total.append(np.mean(total))
+        out[name] = total
+    return out
+
+
+def assd_val(y_pred, y_true, C=None, *, voxelspacing=None, connectivity=1):
+    """average symmetric surface distance per label 1..C and their mean (reference Baseline methods/RDN/utils.py:94-100)"""
+    return surface_vals(y_pred, y_true, C, voxelspacing=voxelspacing, connectivity=connectivity)["assd"]
+
+
+def hd_val(y_pred, y_true, C=None, *, voxelspacing=None, connectivity=1):
+    """Hausdorff distance per label 1..C and their mean (reference Baseline methods/RDN/utils.py:102-108)"""
+    return surface_vals(y_pred, y_true, C, voxelspacing=voxelspacing, connectivity=connectivity)["hd"]
+
+
+def hd95_val(y_pred, y_true, C=None, *, voxelspacing=None, connectivity=1):
+    """95th-percentile Hausdorff distance per label 1..C and their mean (reference Baseline methods/RDN/utils.py:110-116)"""
+    return surface_vals(y_pred, y_true, C, voxelspacing=voxelspacing, connectivity=connectivity)["hd95"]
+
+
+def surface_val_VOI(y_pred, y_true, nlabels=54):
+    """{"hd95", "assd", "hd", "n_skipped"}: each metric's mean over the labels 1..nlabels present in BOTH maps, and how many labels
+    were left out because one map lacks them (a small structure can vanish under a nearest-neighbour warp; that must not end an
+    evaluation run).  All labels missing: the means are NaN.  Inputs as _label_volume takes them, e.g. (1,1,D,H,W) label tensors."""
+    metrics, counts = _surface_tables(y_pred, y_true, nlabels)
+    present = (counts[:, 0] > 0) & (counts[:, 1] > 0)
+    out = {name: (float(np.mean(metrics[present, col])) if present.any() else float("nan")) for name, col in _SURFACE_COLUMN.items()}
+    out["n_skipped"] = int((~present).sum())
+    return out
