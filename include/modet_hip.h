@@ -393,8 +393,11 @@ int modet_proj_ln_bwd_pair_t(const void* x1, int x1_bf16, const float* d_y1, flo
                              float eps, modet_stream_t stream);
 
 /* SpatialTransformer (models.py:25-67; utils.py:30-83 for mode 1):
- *   out[b,p,c] = sample(src[b,:,c], p + flow[b,p,:]), zero padding, voxel coordinates
- *   (the reference's normalise -> grid_sample(align_corners=True) round trip is the identity).
+ *   out[b,p,c] = sample(src[b,:,c], p + flow[b,p,:]), zero padding, DIRECT voxel coordinates: the base corner is
+ *   floor(p + flow) (so the derivative at an integer coordinate is the right-hand one), the nearest mode rounds ties to even.
+ *   The reference's normalise -> grid_sample(align_corners=True) round trip is the identity in exact arithmetic only: in fp32,
+ *   at an exact tie or on an exact integer coordinate, the reference's own round trip may land on either side.  The library
+ *   does not imitate that; tests/test_gpu_warp_exact.py pins the rule stated here, bit for bit, on lattice flows.
  * src,out (B,D,H,W,C); flow (B,D,H,W,3) channels-last, component a = displacement along axis a.
  * mode 0 = trilinear, 1 = nearest (round half to even, as ATen's nearbyint).
  * add_flow=1 (needs C==3): out = warp(src,flow) + flow, the composition of models.py:392,:398,:403,:408.
