@@ -181,6 +181,12 @@ FAMILIES = {
         "modet_surface_ws_bytes": (SZ, [I, I, I, I]),
         "modet_surface_distances": (I, [P, P, P, P, P, SZ, I, I, I, I, F, P]),
     }),
+    "posenc": (_header("modet_hip_posenc.h"), {
+        "modet_posenc_ws_bytes": (SZ, [I, I, I, I, I, I]),
+        "modet_posenc_fwd_pair": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+        "modet_posenc_bwd_data_pair": (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
+        "modet_posenc_bwd_params_pair": (I, [P, P, P, P, P, P, P, P, P, SZ, I, I, I, I, I, I, P]),
+    }),
 }
 # The names a family's entry had before the registry.  Nothing in this tree uses them; they stay because the previous revision's
 # test files, which every change is also run against, reach the library through them (about 95 test ids).  Views of FAMILIES:

@@ -3,7 +3,7 @@
 
 extern "C" {
 
-int modet_hip_version(void) { return 444;
+int modet_hip_version(void) { return 445;
   /* 0.4.0: + modet_conv3d_kernel_family_v, conv kernel family 4 (conv_wgrad_tr_kernel); no environment reads in product builds
      0.4.1: + typed (fp32 | bf16) entry points modet_na_{fwd,bwd}_t, modet_proj_ln_*_t, modet_warp_*_t, modet_warp_fwd_o16,
               modet_avgpool2_fwd_x16, modet_instnorm_*_pool_bf16; modet_ncc_*_box (any window); conv kernel family 5 (conv_q_kernel)
@@ -30,7 +30,10 @@ int modet_hip_version(void) { return 444;
      0.4.4.3: + modet_vecint_fwd, modet_vecint_ws_bytes, modet_vecint_bwd (include/modet_hip_vecint.h): scaling and squaring of a
               velocity field, one launch per step; the backward of a step bounded by one voxel is one gather without atomics
      0.4.4.4: + modet_surface_ws_bytes, modet_surface_distances (include/modet_hip_surface.h): Hausdorff, percentile Hausdorff and
-              average symmetric surface distance per label of two label maps, exact integer squared distances, no read-back */ }
+              average symmetric surface distance per label of two label maps, exact integer squared distances, no read-back
+     0.4.4.5: + modet_posenc_ws_bytes, modet_posenc_fwd_pair, modet_posenc_bwd_data_pair, modet_posenc_bwd_params_pair
+              (include/modet_hip_posenc.h): Linear(Cin -> 6) + alpha * sinusoidal position embedding from a caller-supplied
+              (cos, sin) table, both uses of a level per launch, parameter gradients by one fixed-order fp64 column sum */ }
 
 const char* modet_hip_strerror(int code) {
   switch (code) {

@@ -41,6 +41,9 @@ class Trainer:
         ``capture()`` captures them as three hipGraphs sharing one memory pool and a step is replay 0 -> all-reduce 0 ->
         replay 1 -> all-reduce 1 -> replay 2 -> all-reduce 2 -> join -> Adam (host enqueue ~0.3 ms, no Python in the step).
         Without it: one all-reduce of the whole 4 MB buffer after backward / after the single graph's replay."""
+        if overlap_allreduce and not getattr(model, "stage_buckets", True):
+            raise RuntimeError(f"Trainer: overlap_allreduce=True cuts the backward at ModeT's three bucket boundaries "
+                               f"(parallel.MODET_BUCKETS); {type(model).__name__} has no such cut: train it with the plain all-reduce")
         self.model = model
         self.lr0, self.max_epoch, self.weights = lr, max_epoch, weights
         self.betas, self.eps, self.group = betas, eps, group

@@ -15,8 +15,7 @@ import os
 import torch
 
 from . import data, utils
-from .models import ModeT
-from .train import _natkey
+from .train import MODELS, _natkey, check_model_args, make_model
 
 
 def make_parser():
@@ -30,13 +29,15 @@ def make_parser():
     ap.add_argument("--int-steps", type=int, default=7, help="scaling-and-squaring steps of --diff")
     ap.add_argument("--surface", action="store_true",
                     help="also report HD95 and ASSD (voxels) of the warped and the raw labels, computed on the GPU")
+    ap.add_argument("--model", choices=MODELS, default="modet", help="the network the checkpoint was trained with (train --model)")
     return ap
 
 
 def main(argv=None):
-    args = make_parser().parse_args(argv)
+    ap = make_parser()
+    args = check_model_args(ap, ap.parse_args(argv))
     img_size = tuple(int(s) for s in args.img_size.split(","))
-    model = ModeT(img_size, head_dim=6, num_heads=[8, 4, 2, 1, 1], scale=1, diff=args.diff, int_steps=args.int_steps)
+    model = make_model(args, img_size)
     if args.model_dir:
         files = sorted(os.listdir(args.model_dir), key=_natkey)
         # weights_only=False: checkpoints written by the reference's train.py carry numpy scalars (see train.py here)

@@ -13,6 +13,9 @@ state_dict compatibility:
   * ``mdtN.grid`` (3,3,3,3) [ModeT] / ``mdtN.v`` (27,3) [ModeT_cu]: kept as buffers, either flavour loads;
   * ``transformer.N.grid``: accepted and dropped on load; not emitted on save unless
     ``legacy_grid_buffers=True`` (then regenerated so the reference can load our checkpoints strictly).
+
+``Im2grid`` (the baseline of "Baseline methods/Im2Grid/models.py", further down) is built from the same launches plus the
+fused ``PositionalEncodingLayer``, with the same state_dict rules.
 """
 from __future__ import annotations
 
@@ -352,7 +355,8 @@ class ModeTransformer(nn.Module):
 class CoTr(nn.Module):
     """Coordinate translator of the Im2Grid baseline ("Baseline methods/Im2Grid/models.py":276-322): the same 3x3x3
     neighbourhood attention with ONE head over all C channels, no bias, no scale -- SURVEY.md 8(f) rank 4: it runs on
-    the attention kernels' generic head-dimension path (C a multiple of 8, up to 128).
+    the attention kernels' generic head-dimension path (C a multiple of 8, up to 128), and at C = 6 -- the width of Im2grid's
+    positional-encoding projections -- on the head-dimension-6 kernels ModeT uses.
 
     ``forward(q, k)``: q, k (B,H,W,T,C) channels-last as in the reference -> expected offset (B,3,H,W,T)."""
 
@@ -367,6 +371,52 @@ class CoTr(nn.Module):
     def forward(self, q, k):
         rpb = torch.zeros(1, 3, 3, 3, dtype=q.dtype, device=q.device)
         return ops.to_ncdhw(ops.neighbourhood_attention(q.contiguous(), k.contiguous(), rpb, 1, 1.0))
+
+    def forward_cl(self, q, k):
+        """``forward`` with the result in the layout the kernel wrote it: the expected offset as (B,H,W,T,3)"""
+        rpb = torch.zeros(1, 3, 3, 3, dtype=q.dtype, device=q.device)
+        return ops.neighbourhood_attention(q.contiguous(), k.contiguous(), rpb, 1, 1.0)
+
+
+class PositionalEncodingLayer(nn.Module):
+    """Linear(Cin -> 6) + alpha * sinusoidal embedding of the voxel's position ("Baseline methods/Im2Grid/models.py":238-274);
+    channels-last (B,D,H,W,C) -> (B,D,H,W,6), one fused kernel (ops.posenc).  Parameters and initial values are the reference's:
+    ``proj.weight`` (6, Cin) and ``proj.bias`` (6) zero, ``alpha`` (1) one.  The (cos, sin) table the kernel reads is a
+    NON-persistent buffer, rebuilt when the grid changes: state dicts hold the three parameters only."""
+
+    def __init__(self, in_channels, dim=6):
+        super().__init__()
+        if dim != ops.POSENC_DIM:
+            raise RuntimeError(f"PositionalEncodingLayer: dim = {dim}: the kernels have dim = {ops.POSENC_DIM} only (the reference's "
+                               f"default, the only value Im2grid uses)")
+        self.proj = _LinearParams(in_channels, dim)
+        with torch.no_grad():
+            self.proj.weight.zero_()
+        self.channels = 2
+        self.alpha = nn.Parameter(torch.ones(1))
+        self.register_buffer("tab", None, persistent=False)
+        self.grid_shape = None
+
+    def prepare(self, grid_shape, device=None):
+        """build the table for a (D,H,W) grid ahead of the first call (no host-to-device copy inside a forward then)"""
+        grid_shape = tuple(int(s) for s in grid_shape)
+        self.tab = ops.posenc_table(*grid_shape, device=self.alpha.device if device is None else device)
+        self.grid_shape = grid_shape
+        return self.tab
+
+    def _table(self, x):
+        if x.dim() != 5:
+            raise RuntimeError(f"PositionalEncodingLayer: expects a channels-last (B,D,H,W,C) tensor, got {tuple(x.shape)}")
+        if self.tab is None or self.grid_shape != tuple(x.shape[1:4]) or self.tab.device != x.device:
+            self.prepare(x.shape[1:4], x.device)
+        return self.tab
+
+    def forward(self, feat):
+        return ops.posenc(feat, self.proj.weight, self.proj.bias, self.alpha, self._table(feat))
+
+    def forward_pair(self, fixed_feat, moving_feat):
+        """(q, k) = (self(fixed_feat), self(moving_feat)): one launch each way, one reduction for the shared parameters"""
+        return ops.posenc_pair(fixed_feat, moving_feat, self.proj.weight, self.proj.bias, self.alpha, self._table(fixed_feat))
 
 
 class Correlation3D(nn.Module):
@@ -599,6 +649,102 @@ class ModeT_cu(ModeT):
                  scale=1, legacy_grid_buffers=False, act_dtype=torch.float32, fused_attention=True, diff=False, int_steps=7):
         super().__init__(inshape, in_channel, channels, head_dim, num_heads, scale, legacy_grid_buffers, act_dtype,
                          fused_attention, diff, int_steps)
+
+
+class Im2grid(nn.Module):
+    """The Im2Grid baseline ("Baseline methods/Im2Grid/models.py":325-386): the shared five-level encoder, and per level a
+    positional-encoding projection of the fixed and the warped moving features, the coordinate translator (one-head 3x3x3
+    neighbourhood attention, no bias, no scale) and the composition of its expected offset with the x2-upsampled flow.  Same
+    constructor arguments, attribute names, ``forward(moving, fixed) -> (y_moved, flow)`` contract and state-dict keys as the
+    reference; ``transformer.N.grid`` is handled as ModeT handles it (``legacy_grid_buffers``).  fp32 only, no ``diff``."""
+
+    stage_buckets = False       # engine.Trainer: the three-stage bucket cut of the overlapped all-reduce is ModeT's
+
+    def __init__(self, inshape=(160, 192, 160), flow_multiplier=1., in_channel=1, channels=4, legacy_grid_buffers=False,
+                 act_dtype=torch.float32, diff=False):
+        super().__init__()
+        if act_dtype != torch.float32:
+            raise RuntimeError(f"Im2grid: act_dtype = {act_dtype}: the positional-encoding kernels are fp32 only (bf16 storage is ModeT's)")
+        if diff:
+            raise RuntimeError("Im2grid: diff=True is not supported (the reference's Im2Grid composes its fields without integration)")
+        why = self.unsupported_shape(inshape)
+        if why is not None:
+            raise RuntimeError("Im2grid: inshape: " + why)
+        c = channels
+        if c < 1 or in_channel < 1 or (2 * c) % 4 != 0 or 32 * c > 128:
+            raise RuntimeError(f"Im2grid: channels = {channels}, in_channel = {in_channel}: the level features have 2..32 x channels "
+                               f"channels and the positional-encoding kernels take a multiple of 4 up to 128")
+        self.flow_multiplier = flow_multiplier
+        self.channels = channels
+        self.inshape = tuple(int(s) for s in inshape)
+        self.act_dtype = act_dtype
+        self.encoder = Encoder(in_channel=in_channel, first_out_channel=c)
+        self.peblock = nn.ModuleList()          # (empty in the reference too: no keys)
+        self.peblock1 = PositionalEncodingLayer(2 * c)
+        self.peblock2 = PositionalEncodingLayer(4 * c)
+        self.peblock3 = PositionalEncodingLayer(8 * c)
+        self.peblock4 = PositionalEncodingLayer(16 * c)
+        self.peblock5 = PositionalEncodingLayer(32 * c)
+        for i, pe in enumerate((self.peblock1, self.peblock2, self.peblock3, self.peblock4, self.peblock5)):
+            pe.prepare([s // 2 ** i for s in self.inshape])
+        self.cotr = CoTr()
+        self.transformer = nn.ModuleList(
+            [SpatialTransformer([s // 2 ** i for s in self.inshape], legacy_grid_buffers=legacy_grid_buffers) for i in range(4)])
+
+    @staticmethod
+    def unsupported_shape(shape):
+        """None, or why a (D,H,W) volume cannot go through the five levels"""
+        shape = tuple(shape)
+        if len(shape) != 3:
+            return f"(D, H, W) expected, got {shape}"
+        if any(int(v) % 16 != 0 for v in shape):
+            return f"every spatial dimension must be a multiple of 16 (four 2x poolings, then x2 upsampling back), got {shape}"
+        if any(int(v) < 32 for v in shape):
+            return (f"every spatial dimension must be at least 32: the coarsest level would have a dimension of 1, where the "
+                    f"positional encoding divides by n - 1 = 0, got {shape}")
+        return None
+
+    def forward(self, moving, fixed):
+        """(y_moved (B,1,D,H,W), flow (B,3,D,H,W)) -- reference models.py:352-386"""
+        y_moved, flow = self.forward_cl(moving, fixed)
+        return ops.to_ncdhw(y_moved), ops.to_ncdhw(flow)
+
+    def forward_cl(self, moving, fixed):
+        """``forward`` with both results channels-last, as the kernels wrote them: y_moved (B,D,H,W,1), flow (B,D,H,W,3)"""
+        if moving.shape != fixed.shape or moving.dim() != 5:
+            raise RuntimeError("Im2grid.forward expects two (B,C,D,H,W) volumes of the same shape")
+        why = self.unsupported_shape(moving.shape[2:])
+        if why is not None:
+            raise RuntimeError("Im2grid.forward: " + why)
+        B = moving.shape[0]
+        mov_cl = ops.to_channels_last(moving.contiguous())
+        fix_cl = ops.to_channels_last(fixed.contiguous())
+        with ops.trace_range("encoder"):
+            M, Fx = self.encoder.forward_pair(ops.cat_batch(mov_cl, fix_cl), B)
+        ST = self.transformer
+
+        def match(lvl, pe, flow):
+            """cotr(pe(F), pe(warp(M, flow))) -> (expected offset w, flow); the returned flow is what the caller composes with
+            (ops.warp_tee adds the composition's gradient inside the feature warp's backward, as in ModeT)"""
+            if flow is None:
+                Mw = M[lvl]
+            else:
+                Mw, flow = ops.warp_tee(M[lvl], flow)
+            q, k = pe.forward_pair(Fx[lvl], Mw)
+            return self.cotr.forward_cl(q, k), flow
+
+        with ops.trace_range("level5"):
+            flow = ops.upsample2(match(4, self.peblock5, None)[0], 2.0)
+        # every w is an expectation over offsets in {-1,0,1}^3: bounded-flow compositions (no atomics), as ModeT's levels 1 and 2
+        for lvl, pe in ((3, self.peblock4), (2, self.peblock3), (1, self.peblock2)):
+            with ops.trace_range("level%d" % (lvl + 1)):
+                w, flow = match(lvl, pe, flow)
+                flow = ops.upsample2(ST[lvl].forward_cl(flow, w, add_flow=True, flow_bound=1), 2.0)
+        with ops.trace_range("level1"):
+            w, flow = match(0, self.peblock1, flow)
+            flow = ST[0].forward_cl(flow, w, add_flow=True, flow_bound=1)
+            y_moved, flow = ops.warp_tee(mov_cl, flow)
+        return y_moved, flow
 
 
 def load_numpy_weights(model: nn.Module, weights) -> None:

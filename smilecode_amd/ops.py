@@ -9,6 +9,7 @@ There is no eager / CPU fallback: a missing library or a non-GPU tensor raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import threading
 
@@ -1186,6 +1187,101 @@ def proj_ln_pair(x1, x2, Wt, b, gamma, beta, eps=1e-5):
 def proj_ln(x, Wt, b, gamma, beta, eps=1e-5):
     """Linear + LayerNorm on channels-last voxels.  reference: ProjectionLayer, models.py:230-241"""
     return _ProjLN.apply(x, Wt, b, gamma, beta, eps)
+
+
+POSENC_DIM = 6                   # MODET_POSENC_DIM of include/modet_hip_posenc.h: the only width the kernels have
+
+
+def posenc_table(D, H, W, device=None):
+    """the (cos, sin) table of include/modet_hip_posenc.h for a (D,H,W) grid, (D+H+W, 2) fp32: row p of an axis of length n holds
+    cos and sin of p * pi / (n - 1), computed in fp64 and rounded once"""
+    rows = []
+    for n in (D, H, W):
+        if int(n) < 2:
+            raise RuntimeError(f"posenc_table: every axis needs at least 2 voxels (p * pi / (n - 1)), got {(D, H, W)}")
+        t = torch.arange(int(n), dtype=torch.float64) * (math.pi / (int(n) - 1))
+        rows.append(torch.stack((t.cos(), t.sin()), -1))
+    return torch.cat(rows).float().to(device).contiguous()
+
+
+def _posenc_args(op, x1, x2, Wt, b, alpha, tab):
+    """x1 (and x2) (B,D,H,W,Cin) fp32; Wt (6,Cin); b (6,); alpha (1,); tab (D+H+W, 2) -> (B, D, H, W, Cin)"""
+    for name, t in (("x1", x1), ("x2", x2)):
+        if t is not None and getattr(t, "data16", None) is not None:
+            raise RuntimeError(f"{op}: {name} is a bf16 feature handle; the positional-encoding kernels are fp32 only")
+    _chk(x1, x2, Wt, b, alpha, tab)
+    _rank5(op, "x1", x1)
+    _same_shape(op, "x2", x2, x1.shape, "x1")
+    B, D, H, W, Cin = x1.shape
+    if Wt.dim() != 2 or Wt.shape[0] != POSENC_DIM:
+        raise RuntimeError(f"{op}: expects a ({POSENC_DIM}, Cin) weight (dim = {POSENC_DIM} only), got {tuple(Wt.shape)}")
+    _same_shape(op, "weight", Wt, (POSENC_DIM, Cin), f"input channels {Cin}")
+    _same_shape(op, "bias", b, (POSENC_DIM,))
+    _same_shape(op, "alpha", alpha, (1,))
+    if B < 1 or min(D, H, W) < 2:
+        raise RuntimeError(f"{op}: needs a batch and at least 2 voxels along every axis (the embedding divides by n - 1), got {tuple(x1.shape)}")
+    _same_shape(op, "tab", tab, (D + H + W, 2), f"posenc_table({D}, {H}, {W})")
+    if Cin % 4 != 0 or not 4 <= Cin <= 128:
+        raise RuntimeError(f"{op}: {Cin} input channels: the kernels take a multiple of 4 up to 128")
+    if _L().modet_posenc_ws_bytes(B, D, H, W, Cin, POSENC_DIM) == 0:
+        raise RuntimeError(f"{op}: no kernel covers the shape {tuple(x1.shape)}")
+    return B, D, H, W, Cin
+
+
+class _PosEncPair(Function):
+    """The positional-encoding projection applied to one or two inputs of one shape with the same parameters (x2 None: one);
+    the backward sums the parameter gradients of both uses in one reduction (modet_posenc_bwd_params_pair)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, Wt, b, alpha, tab):
+        B, D, H, W, Cin = _posenc_args("posenc_pair" if x2 is not None else "posenc", x1, x2, Wt, b, alpha, tab)
+        N, uses = B * D * H * W, 1 if x2 is None else 2
+        ys = [None if x is None else torch.empty(x.shape[:-1] + (POSENC_DIM,), dtype=torch.float32, device=x.device) for x in (x1, x2)]
+        with _Guard(x1, f"posenc_fwd[{Cin}]", uses * N * (12.0 * Cin + 18.0), 4.0 * uses * N * (Cin + POSENC_DIM)):
+            _call(_L().modet_posenc_fwd_pair, _p(x1), _p(x2), _p(Wt), _p(b), _p(alpha), _p(tab), _p(ys[0]), _p(ys[1]), B, D, H, W, Cin,
+                  POSENC_DIM, _stream())
+        ctx.save_for_backward(x1, x2, Wt, b, alpha, tab)
+        ctx.step = current_step()
+        return ys[0], ys[1]
+
+    @staticmethod
+    def backward(ctx, dy1, dy2):
+        x1, x2, Wt, b, alpha, tab = ctx.saved_tensors
+        B, D, H, W, Cin = x1.shape
+        N, uses, L = B * D * H * W, 1 if x2 is None else 2, _L()
+        dy1 = dy1.contiguous()
+        dy2 = None if x2 is None else dy2.contiguous()
+        dims = (B, D, H, W, Cin, POSENC_DIM)
+        dx1 = torch.empty_like(x1) if ctx.needs_input_grad[0] else None
+        dx2 = torch.empty_like(x2) if (x2 is not None and ctx.needs_input_grad[1]) else None
+        if dx1 is not None or dx2 is not None:
+            n = (dx1 is not None) + (dx2 is not None)
+            with _Guard(x1, f"posenc_bwd_data[{Cin}]", n * N * 12.0 * Cin, 4.0 * n * N * (Cin + POSENC_DIM)):
+                _call(L.modet_posenc_bwd_data_pair, _p(dy1), _p(dy2), _p(Wt), _p(dx1), _p(dx2), *dims, _stream())
+        ret = [None, None, None]
+        if any(ctx.needs_input_grad[2:5]):
+            # written straight into the step's gradient buffer where the scope hands out destinations; the launch reduces its own
+            # partial rows (it does not join the scope's leaf-reduction launch: DESIGN.md 4.10)
+            (dW, db, da), _, ret = _param_dsts(ctx.step, Wt, b, alpha)
+            nb = L.modet_posenc_ws_bytes(*dims)
+            ws = _ws(nb, x1)
+            with _Guard(x1, f"posenc_bwd_params[{Cin}]", uses * N * (12.0 * Cin + 24.0), 4.0 * uses * N * (Cin + POSENC_DIM)):
+                _call(L.modet_posenc_bwd_params_pair, _p(x1), _p(dy1), _p(x2), _p(dy2), _p(tab), _p(dW), _p(db), _p(da), _p(ws), nb,
+                      *dims, _stream())
+        return (dx1, dx2, *ret, None)
+
+
+def posenc_pair(x1, x2, Wt, b, alpha, tab):
+    """(layer(x1), layer(x2)) for the reference's PositionalEncodingLayer with shared parameters -- Im2Grid's q / k of a level
+    ("Baseline methods/Im2Grid/models.py":360-380); tab = posenc_table(D, H, W)"""
+    if x2 is None:
+        raise RuntimeError("posenc_pair: x2 is missing (ops.posenc is the single-input form)")
+    return _PosEncPair.apply(x1, x2, Wt, b, alpha, tab)
+
+
+def posenc(x, Wt, b, alpha, tab):
+    """Linear(Cin -> 6) + alpha * sinusoidal position embedding on channels-last voxels (PositionalEncodingLayer, models.py:238-274)"""
+    return _PosEncPair.apply(x, None, Wt, b, alpha, tab)[0]
 
 
 def _na_args(op, C, heads, rpb, bf16):

@@ -4,6 +4,7 @@
     python -m smilecode_amd.train --train-dir /LPBA_path/Train/ --val-dir /LPBA_path/Val/
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m smilecode_amd.train ...
     python -m smilecode_amd.train --synthetic 4 --img-size 64,64,64 --max-epoch 1      # no data needed
+    python -m smilecode_amd.train --model im2grid ...      # the Im2Grid baseline ("Baseline methods/Im2Grid/train.py"), its directory name
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ import torch
 from . import data, utils
 from .engine import Trainer, poly_lr
 from .losses import REG_TERMS, SIM_TERMS
-from .models import ModeT
+from .models import Im2grid, ModeT
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
 
@@ -69,6 +70,9 @@ def latest_checkpoint(model_dir):
     return os.path.join(model_dir, files[-1])
 
 
+MODELS = ("modet", "im2grid")       # --model of train.py and infer.py
+
+
 def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--train-dir", default="/LPBA_path/Train/")
@@ -101,20 +105,42 @@ def make_parser():
                     help="diffeomorphic variant: every level's field is integrated by scaling and squaring (VecInt) before it is "
                          "composed, as the reference's RDN_diff models do; same parameters, so checkpoints are interchangeable")
     ap.add_argument("--int-steps", type=int, default=7, help="scaling-and-squaring steps of --diff (the reference's VecInt default)")
+    ap.add_argument("--model", choices=MODELS, default="modet",
+                    help="the network: ModeT, or the Im2Grid baseline the paper compares it with (positional-encoding projection + "
+                         "coordinate translator per level; fp32, no --diff, no --overlap-allreduce)")
     return ap
+
+
+def check_model_args(ap, args):
+    """argument combinations a network does not have end as argument errors, before anything is built"""
+    if args.model == "im2grid":
+        if args.diff:
+            ap.error("--diff is ModeT's: the Im2Grid baseline composes its fields without integration")
+        if getattr(args, "overlap_allreduce", False):
+            ap.error("--overlap-allreduce is ModeT's: the three-stage bucket cut follows ModeT's layers")
+    return args
+
+
+def make_model(args, img_size):
+    if args.model == "im2grid":
+        return Im2grid(img_size)
+    return ModeT(img_size, head_dim=6, num_heads=[8, 4, 2, 1, 1], scale=1, diff=args.diff, int_steps=args.int_steps)
 
 
 def save_dir_name(args, num_heads, head_dim, weights):
     """the experiment directory: the reference's name (train.py:66-68) with the similarity term in it; a regulariser other than
     the default Grad3d with weight 1 is named too, the default leaves the name as it always was; --diff adds a suffix"""
     reg = "" if (args.reg == "grad3d" and weights[1] == 1) else "{}_".format(args.reg)
+    if getattr(args, "model", "modet") == "im2grid":        # the reference's "Baseline methods/Im2Grid/train.py":49, the terms named alike
+        return "Im2Grid_{}_{}_reg_{}{}_lr_{}_54r/".format(args.sim, weights[0], reg, weights[1], args.lr)
     diff = "_diff{}".format(args.int_steps) if getattr(args, "diff", False) else ""
     return "modet-heads({}{}{}{}{})-rpe_headim_{}_{}_{}_reg_{}{}_lr_{}_54r{}/".format(*num_heads, head_dim, args.sim, weights[0], reg,
                                                                                      weights[1], args.lr, diff)
 
 
 def main(argv=None):
-    args = make_parser().parse_args(argv)
+    ap = make_parser()
+    args = check_model_args(ap, ap.parse_args(argv))
     same_seeds(24)
     rank, local, world = init_from_env()
     torch.cuda.set_device(local)
@@ -131,7 +157,7 @@ def main(argv=None):
         sys.stdout = Logger(log_dir)
         f = open(os.path.join(log_dir, "losses and dice.txt"), "a")
 
-    model = ModeT(img_size, head_dim=head_dim, num_heads=num_heads, scale=1, diff=args.diff, int_steps=args.int_steps).cuda()
+    model = make_model(args, img_size).cuda()
     best_dsc = 0
     resume = None
     if args.cont_training:
