@@ -187,6 +187,14 @@ FAMILIES = {
         "modet_posenc_bwd_data_pair": (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
         "modet_posenc_bwd_params_pair": (I, [P, P, P, P, P, P, P, P, P, SZ, I, I, I, I, I, I, P]),
     }),
+    "convs2": (_header("modet_hip_convs2.h"), {
+        "modet_convs2_ws_bytes": (SZ, [I, I, I, I, I, I, I]),
+        "modet_convs2_fwd": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, I, F, P]),
+        "modet_convs2_bwd_data": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, I, F, P]),
+        "modet_convs2_bwd_weight": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, I, I, F, P]),
+        "modet_cat_channels2_fwd": (I, [P, P, P, I64, I, I, P]),
+        "modet_cat_channels2_bwd": (I, [P, P, P, I64, I, I, P]),
+    }),
 }
 # The names a family's entry had before the registry.  Nothing in this tree uses them; they stay because the previous revision's
 # test files, which every change is also run against, reach the library through them (about 95 test ids).  Views of FAMILIES:

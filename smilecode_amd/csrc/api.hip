@@ -3,7 +3,7 @@
 
 extern "C" {
 
-int modet_hip_version(void) { return 445;
+int modet_hip_version(void) { return 446;
   /* 0.4.0: + modet_conv3d_kernel_family_v, conv kernel family 4 (conv_wgrad_tr_kernel); no environment reads in product builds
      0.4.1: + typed (fp32 | bf16) entry points modet_na_{fwd,bwd}_t, modet_proj_ln_*_t, modet_warp_*_t, modet_warp_fwd_o16,
               modet_avgpool2_fwd_x16, modet_instnorm_*_pool_bf16; modet_ncc_*_box (any window); conv kernel family 5 (conv_q_kernel)
@@ -33,7 +33,11 @@ int modet_hip_version(void) { return 445;
               average symmetric surface distance per label of two label maps, exact integer squared distances, no read-back
      0.4.4.5: + modet_posenc_ws_bytes, modet_posenc_fwd_pair, modet_posenc_bwd_data_pair, modet_posenc_bwd_params_pair
               (include/modet_hip_posenc.h): Linear(Cin -> 6) + alpha * sinusoidal position embedding from a caller-supplied
-              (cos, sin) table, both uses of a level per launch, parameter gradients by one fixed-order fp64 column sum */ }
+              (cos, sin) table, both uses of a level per launch, parameter gradients by one fixed-order fp64 column sum
+     0.4.4.6: + modet_convs2_ws_bytes, modet_convs2_fwd, modet_convs2_bwd_data, modet_convs2_bwd_weight, modet_cat_channels2_fwd,
+              modet_cat_channels2_bwd (include/modet_hip_convs2.h): the 3x3x3 convolution with stride 2 and a fused LeakyReLU(slope)
+              of the RDN / PCNet / PR++ encoders (fp32 on any input range; gather data gradient, weight gradient by partial rows and
+              one fixed-order fp64 column sum) and the two-tensor channel concatenation */ }
 
 const char* modet_hip_strerror(int code) {
   switch (code) {

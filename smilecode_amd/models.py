@@ -15,7 +15,8 @@ state_dict compatibility:
     ``legacy_grid_buffers=True`` (then regenerated so the reference can load our checkpoints strictly).
 
 ``Im2grid`` (the baseline of "Baseline methods/Im2Grid/models.py", further down) is built from the same launches plus the
-fused ``PositionalEncodingLayer``, with the same state_dict rules.
+fused ``PositionalEncodingLayer``, with the same state_dict rules.  ``RDN`` (the baseline of "Baseline methods/RDN/models.py", at
+the end) adds the stride-2 encoder convolution (``ops.conv3d_s2``) and the Estimator on the stride-1 convolutions.
 """
 from __future__ import annotations
 
@@ -745,6 +746,195 @@ class Im2grid(nn.Module):
             flow = ST[0].forward_cl(flow, w, add_flow=True, flow_bound=1)
             y_moved, flow = ops.warp_tee(mov_cl, flow)
         return y_moved, flow
+
+
+class ConvBlockS2(nn.Module):
+    """nn.Conv3d(cin, cout, 3, stride=2, padding=1) + LeakyReLU(alpha) ("Baseline methods/RDN/models.py":120-134 as its Encoder
+    calls it, :181-184); channels-last in/out, one fused kernel (ops.conv3d_s2)."""
+
+    def __init__(self, in_channels, out_channels, alpha=0.2):
+        super().__init__()
+        self.main = _Conv3dParams(in_channels, out_channels)
+        self.alpha = float(alpha)
+
+    def forward(self, x):
+        return ops.conv3d_s2(x, self.main.weight, self.main.bias, self.alpha)
+
+
+class EncoderS2(nn.Module):
+    """RDN's encoder ("Baseline methods/RDN/models.py":172-192): four stride-2 ConvBlocks, c, 2c, 4c, 8c channels at 1/2 .. 1/16"""
+
+    def __init__(self, in_channel=1, first_out_channel=16):
+        super().__init__()
+        c = first_out_channel
+        self.conv0 = ConvBlockS2(in_channel, c)
+        self.conv1 = ConvBlockS2(c, 2 * c)
+        self.conv2 = ConvBlockS2(2 * c, 4 * c)
+        self.conv3 = ConvBlockS2(4 * c, 8 * c)
+
+    def forward(self, x):
+        out0 = self.conv0(x)
+        out1 = self.conv1(out0)
+        out2 = self.conv2(out1)
+        out3 = self.conv3(out2)
+        return [out0, out1, out2, out3]
+
+
+class Estimator(nn.Module):
+    """RDN's flow estimator ("Baseline methods/RDN/models.py":195-214): three stride-1 convolutions c -> c, LeakyReLU(0.1), and a
+    convolution to 3 channels, over the channel concatenation [fixed; moving].  ``conv`` keeps nn.Sequential's indices 0, 1, 2, 4
+    (3 is the activation, fused into the third convolution here).  The flow convolution starts as Normal(0, 1e-5) with zero bias."""
+
+    def __init__(self, channel):
+        super().__init__()
+        c = channel
+        self.conv = nn.ModuleList([_Conv3dParams(c, c), _Conv3dParams(c, c), _Conv3dParams(c, c), nn.Identity(), _Conv3dParams(c, 3)])
+        with torch.no_grad():
+            self.conv[4].weight.normal_(0.0, 1e-5)
+            self.conv[4].bias.zero_()
+
+    def forward(self, fixed_fm, moving_fm):
+        x = ops.cat_channels(fixed_fm, moving_fm)
+        x = ops.conv3d(x, self.conv[0].weight, self.conv[0].bias, False)
+        x = ops.conv3d(x, self.conv[1].weight, self.conv[1].bias, False)
+        x = ops.conv3d(x, self.conv[2].weight, self.conv[2].bias, True)         # (ops.LRELU_SLOPE = 0.1: the Estimator's alpha)
+        return ops.conv3d(x, self.conv[4].weight, self.conv[4].bias, False)
+
+
+RDN_MAX_ESTIMATOR_WIDTH = 256       # the widest stride-1 convolution an Estimator runs is 16 x channels (csrc/conv3d.hip: Cout <= 256)
+
+
+def rdn_unsupported_config(in_channel=1, channels=16):
+    """None if every kernel on RDN's path accepts the channel counts, else a message naming the argument (the library is asked for
+    the stride-2 layers; the stride-1 limits are restated next to a pointer at the kernel's own check)"""
+    if int(in_channel) != in_channel or int(channels) != channels or in_channel < 1 or channels < 1:
+        return f"in_channel = {in_channel}, channels = {channels}: both must be positive integers"
+    L = ops._L()
+    c = channels
+    for cin, cout in [(in_channel, c), (c, 2 * c), (2 * c, 4 * c), (4 * c, 8 * c)]:
+        if L.modet_convs2_ws_bytes(1, 16, 16, 16, cin, cout, 0) == 0:
+            arg = "in_channel" if cin == in_channel and cout == c and not (in_channel == 1 or in_channel % 4 == 0) else "channels"
+            return (f"{arg} = {in_channel if arg == 'in_channel' else channels}: the encoder's stride-2 layer {cin} -> {cout} is refused "
+                    f"(the convs2 kernels take 1 or a multiple of 4 input channels and a multiple of 4 output channels, up to "
+                    f"{ops.CONVS2_MAX_CHANNELS})")
+    if 16 * c > RDN_MAX_ESTIMATOR_WIDTH:
+        return (f"channels = {channels}: the level-4 Estimator convolves {16 * c} -> {16 * c} channels; the stride-1 kernels take up to "
+                f"{RDN_MAX_ESTIMATOR_WIDTH}")
+    return None
+
+
+class RDN(nn.Module):
+    """The RDN baseline ("Baseline methods/RDN/models.py":434-615, RDN / RDN_test) and with ``diff=True`` its diffeomorphic form
+    (:323-432, :884-978, RDN_diff / RDN_diff_test): a four-level stride-2 encoder shared by both images, and per level
+    ``level_recursion[l]`` passes of an Estimator over [fixed; warp(moving, sflow)] whose output w is composed with the stage flow,
+    ``sflow = ST(sflow, w) + w``, between x2 upsamplings.  Same constructor arguments, attribute names and state-dict keys as the
+    reference (``encoder.convN.main.*``, ``estN.<stage>.conv.{0,1,2,4}.*``; ``transformer.N.grid`` and
+    ``integrate.N.transformer.grid`` as ModeT handles them, ``legacy_grid_buffers``).  ``forward(moving, fixed)`` returns
+    ``(y_moved, flow_out)``, with ``return_stage_flows=True`` the reference's training tuple ``(y_moved, flow_out, *sflows)``
+    (``*svs``, the composed velocities, with ``diff=True``).  fp32 only; one stage."""
+
+    stage_buckets = False       # engine.Trainer: the three-stage bucket cut of the overlapped all-reduce is ModeT's
+
+    def __init__(self, inshape=(160, 192, 160), in_channel=1, channels=16, stage_recursion=1, level_recursion=[1, 1, 1, 1],
+                 diff=False, int_steps=7, return_stage_flows=False, legacy_grid_buffers=False, act_dtype=torch.float32):
+        super().__init__()
+        if act_dtype != torch.float32:
+            raise RuntimeError(f"RDN: act_dtype = {act_dtype}: the stride-2 convolution kernels are fp32 only (bf16 storage is ModeT's)")
+        if isinstance(stage_recursion, bool) or not isinstance(stage_recursion, int) or stage_recursion < 1:
+            raise RuntimeError(f"RDN: stage_recursion = {stage_recursion!r}: a positive integer")
+        if stage_recursion > 1:
+            raise RuntimeError(f"RDN: stage_recursion = {stage_recursion}: a second stage warps the features by the flow downsampled "
+                               f"trilinearly by 1/2, 1/4 and 1/8 (the reference's ResizeTransform / interpolate), which is not built; "
+                               f"only stage_recursion = 1 is supported")
+        levels = list(level_recursion)
+        if len(levels) != 4 or any(isinstance(v, bool) or int(v) != v or v < 1 for v in levels):
+            raise RuntimeError(f"RDN: level_recursion = {level_recursion}: four positive pass counts, finest level first")
+        why = self.unsupported_shape(inshape)
+        if why is not None:
+            raise RuntimeError("RDN: inshape: " + why)
+        why = rdn_unsupported_config(in_channel, channels)
+        if why is not None:
+            raise RuntimeError("RDN: " + why)
+        self.channels = channels
+        self.step = 7
+        self.inshape = tuple(int(s) for s in inshape)
+        self.stages = stage_recursion
+        self.levels = [int(v) for v in levels]
+        self.diff = bool(diff)
+        self.int_steps = int_steps
+        self.return_stage_flows = bool(return_stage_flows)
+        self.act_dtype = act_dtype
+        c = channels
+        self.encoder = EncoderS2(in_channel=in_channel, first_out_channel=c)
+        self.est3 = nn.ModuleList([Estimator(2 * 8 * c) for _ in range(self.stages)])
+        self.est2 = nn.ModuleList([Estimator(2 * 4 * c) for _ in range(self.stages)])
+        self.est1 = nn.ModuleList([Estimator(2 * 2 * c) for _ in range(self.stages)])
+        self.est0 = nn.ModuleList([Estimator(2 * c) for _ in range(self.stages)])
+        self.transformer = nn.ModuleList(
+            [SpatialTransformer([s // 2 ** i for s in self.inshape], legacy_grid_buffers=legacy_grid_buffers) for i in range(5)])
+        if self.diff:
+            self.integrate = nn.ModuleList(
+                [VecInt([s // 2 ** i for s in self.inshape], int_steps, legacy_grid_buffers=legacy_grid_buffers) for i in range(5)])
+
+    @staticmethod
+    def unsupported_shape(shape):
+        """None, or why a (D,H,W) volume cannot go through the four levels"""
+        shape = tuple(shape)
+        if len(shape) != 3:
+            return f"(D, H, W) expected, got {shape}"
+        if any(int(v) % 16 != 0 for v in shape):
+            return f"every spatial dimension must be a multiple of 16 (four stride-2 layers, then x2 upsampling back), got {shape}"
+        if any(int(v) < 32 for v in shape):
+            return f"every spatial dimension must be at least 32 (the coarsest level would have a dimension of 1), got {shape}"
+        return None
+
+    def forward(self, moving, fixed):
+        """(y_moved (B,1,D,H,W), flow_out (B,3,D,H,W)[, the stage flow (B,3,D/2,H/2,W/2)]) -- reference models.py:465-525"""
+        return tuple(ops.to_ncdhw(t) for t in self._run(moving, fixed, self.return_stage_flows))
+
+    def forward_cl(self, moving, fixed):
+        """``forward`` with the results channels-last, as the kernels wrote them: y_moved (B,D,H,W,1), flow_out (B,D,H,W,3)"""
+        return self._run(moving, fixed, self.return_stage_flows)
+
+    def _run(self, moving, fixed, stage_flows):
+        if moving.shape != fixed.shape or moving.dim() != 5:
+            raise RuntimeError("RDN.forward expects two (B,C,D,H,W) volumes of the same shape")
+        why = self.unsupported_shape(moving.shape[2:])
+        if why is not None:
+            raise RuntimeError("RDN.forward: " + why)
+        B = moving.shape[0]
+        mov_cl = ops.to_channels_last(moving.contiguous())
+        fix_cl = ops.to_channels_last(fixed.contiguous())
+        with ops.trace_range("encoder"):            # the shared encoder on both images as one batch (no layer mixes samples)
+            feats = self.encoder(ops.cat_batch(mov_cl, fix_cl))
+            M, Fx = zip(*(_SplitBatch.apply(f, B) for f in feats))
+        ST = self.transformer
+        ests = (self.est0[0], self.est1[0], self.est2[0], self.est3[0])
+        sflow = sv = None
+        for lvl in (3, 2, 1, 0):                    # features of level lvl sit on the grid of transformer[lvl + 1]
+            with ops.trace_range("level%d" % (lvl + 1)):
+                if sflow is not None:
+                    sflow = ops.upsample2(sflow, 2.0)
+                    if self.diff:
+                        sv = ops.upsample2(sv, 2.0)
+                for j in range(self.levels[lvl]):
+                    if sflow is None:               # level 4, first pass: no warp and no composition
+                        w = ests[lvl](Fx[lvl], M[lvl])
+                        sflow, sv = (self.integrate[lvl + 1].forward_cl(w), w) if self.diff else (w, None)
+                        continue
+                    # the stage flow has a second consumer (the composition): warp_tee adds that gradient in its own backward
+                    Mw, sflow = ops.warp_tee(M[lvl], sflow)
+                    w = ests[lvl](Fx[lvl], Mw)
+                    if self.diff:
+                        sv = ST[lvl + 1].forward_cl(sv, w, add_flow=True)
+                        w = self.integrate[lvl + 1].forward_cl(w)
+                    sflow = ST[lvl + 1].forward_cl(sflow, w, add_flow=True)
+        with ops.trace_range("output"):
+            flow_out = ops.upsample2(sflow, 2.0)
+            y_moved, flow_out = ops.warp_tee(mov_cl, flow_out)      # (the flow's other consumer: the caller, Grad3d in training)
+        if stage_flows:
+            return y_moved, flow_out, (sv if self.diff else sflow)
+        return y_moved, flow_out
 
 
 def load_numpy_weights(model: nn.Module, weights) -> None:

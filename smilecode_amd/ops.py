@@ -1284,6 +1284,133 @@ def posenc(x, Wt, b, alpha, tab):
     return _PosEncPair.apply(x, None, Wt, b, alpha, tab)[0]
 
 
+CONVS2_MAX_CHANNELS = 256        # MODET_CONVS2_MAX_CHANNELS of include/modet_hip_convs2.h
+
+
+def conv3d_s2_out_shape(D, H, W):
+    """the output grid of a 3x3x3 convolution with stride 2 and padding 1: (n - 1) // 2 + 1 per axis"""
+    return tuple((int(n) - 1) // 2 + 1 for n in (D, H, W))
+
+
+def _convs2_args(op, x, w, b, slope):
+    """x (B,D,H,W,Cin); w (Cout,Cin,3,3,3); b (Cout,) or None; slope None or a float >= 0 -> (B, D, H, W, Cin, Cout, act, slope)"""
+    if getattr(x, "data16", None) is not None:
+        raise RuntimeError(f"{op}: x is a bf16 feature handle; the stride-2 convolution kernels are fp32 only")
+    _chk(x, w, b)
+    _rank5(op, "x", x)
+    if w.dim() != 5:
+        raise RuntimeError(f"{op}: weight must be (Cout,Cin,3,3,3), got {tuple(w.shape)}")
+    B, D, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    _same_shape(op, "weight", w, (Cout, Cin, 3, 3, 3), f"x {tuple(x.shape)}")
+    _same_shape(op, "bias", b, (Cout,), f"weight {tuple(w.shape)}")
+    if slope is not None and not (isinstance(slope, (int, float)) and not isinstance(slope, bool) and slope >= 0.0):
+        raise RuntimeError(f"{op}: slope must be None (no activation) or a number >= 0 (0.0: ReLU), got {slope!r}")
+    if not (Cin == 1 or (Cin % 4 == 0 and Cin >= 4)) or Cin > CONVS2_MAX_CHANNELS:
+        raise RuntimeError(f"{op}: x has {Cin} channels: the kernels take 1 or a multiple of 4 up to {CONVS2_MAX_CHANNELS}")
+    if Cout % 4 != 0 or not 4 <= Cout <= CONVS2_MAX_CHANNELS:
+        raise RuntimeError(f"{op}: weight has {Cout} output channels: the kernels take a multiple of 4 up to {CONVS2_MAX_CHANNELS}")
+    if min(B, D, H, W) < 1:
+        raise RuntimeError(f"{op}: x {tuple(x.shape)} is empty")
+    if _L().modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, 0) == 0:
+        raise RuntimeError(f"{op}: x {tuple(x.shape)} -> {Cout} channels: a tensor of 2^31 elements or more (the kernels' limit)")
+    return B, D, H, W, Cin, Cout, int(slope is not None), float(slope or 0.0)
+
+
+class _Conv3dS2(Function):
+    """nn.Conv3d(Cin, Cout, 3, stride=2, padding=1) [+ LeakyReLU(slope)] on channels-last voxels; the backward folds the
+    activation's derivative into its d_y loads and skips the data gradient of an input that needs none (the image)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, slope):
+        B, D, H, W, Cin, Cout, act, sl = _convs2_args("conv3d_s2", x, w, b, slope)
+        L = _L()
+        Do, Ho, Wo = conv3d_s2_out_shape(D, H, W)
+        y = torch.empty((B, Do, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
+        nb = L.modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, 0)
+        ws = _ws(nb, x)
+        with _Guard(x, f"convs2_fwd[{Cin}->{Cout}]", 54.0 * Cin * Cout * B * Do * Ho * Wo, 4.0 * (x.numel() + y.numel())):
+            _call(L.modet_convs2_fwd, _p(x), _p(w), _p(b), _p(y), _p(ws), nb, B, D, H, W, Cin, Cout, act, sl, _stream())
+        ctx.save_for_backward(x, w, b, y if act else None)
+        ctx.act, ctx.slope, ctx.step = act, sl, current_step()
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b, y = ctx.saved_tensors
+        B, D, H, W, Cin = x.shape
+        Cout, L = w.shape[0], _L()
+        dy = dy.contiguous()
+        dims = (B, D, H, W, Cin, Cout, ctx.act, ctx.slope)
+        n_out = float(dy.numel() // Cout)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            nb = L.modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, 1)
+            ws = _ws(nb, x)
+            with _Guard(x, f"convs2_bwd_data[{Cout}->{Cin}]", 54.0 * Cin * Cout * n_out, 4.0 * (x.numel() + (1 + ctx.act) * dy.numel())):
+                _call(L.modet_convs2_bwd_data, _p(dy), _p(y), _p(w), _p(dx), _p(ws), nb, *dims, _stream())
+        ret = [None, None]
+        if ctx.needs_input_grad[1] or (b is not None and ctx.needs_input_grad[2]):
+            # written straight into the step's gradient buffer where the scope hands out destinations; the launch reduces its own
+            # partial rows (DESIGN.md 4.11)
+            params = (w,) if b is None else (w, b)
+            dsts, _, back = _param_dsts(ctx.step, *params)
+            ret = list(back) + [None] * (2 - len(back))
+            nb = L.modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, 2)
+            ws = _ws(nb, x)
+            with _Guard(x, f"convs2_bwd_weight[{Cin}->{Cout}]", 54.0 * Cin * Cout * n_out, 4.0 * (x.numel() + (1 + ctx.act) * dy.numel())):
+                _call(L.modet_convs2_bwd_weight, _p(x), _p(dy), _p(y), _p(dsts[0]), _p(dsts[1] if b is not None else None), _p(ws), nb,
+                      *dims, _stream())
+        return (dx, ret[0], ret[1], None)
+
+
+def conv3d_s2(x, w, b=None, slope=None):
+    """3x3x3 convolution with stride 2 and padding 1 on channels-last voxels, then LeakyReLU(slope) (slope=None: no activation,
+    0.0: ReLU) -- the ConvBlock(cin, cout, 3, 2, 1) of the RDN / PCNet / PR++ encoders ("Baseline methods/RDN/models.py":172-192).
+    x (B,D,H,W,Cin) -> (B,Do,Ho,Wo,Cout), conv3d_s2_out_shape."""
+    return _Conv3dS2.apply(x, w, b, slope)
+
+
+class _CatChannels(Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        for name, t in (("a", a), ("b", b)):
+            if getattr(t, "data16", None) is not None:
+                raise RuntimeError(f"cat_channels: {name} is a bf16 feature handle; the concatenation kernels are fp32 only")
+        _chk(a, b)
+        if a.dim() < 2 or b.dim() != a.dim() or tuple(a.shape[:-1]) != tuple(b.shape[:-1]):
+            raise RuntimeError(f"cat_channels: a {tuple(a.shape)} and b {tuple(b.shape)} must agree in every dimension but the last")
+        C1, C2 = a.shape[-1], b.shape[-1]
+        N = a.numel() // max(C1, 1)
+        if N < 1 or C1 < 1 or C2 < 1:
+            raise RuntimeError(f"cat_channels: a {tuple(a.shape)} or b {tuple(b.shape)} is empty")
+        if N * (C1 + C2) >= 2 ** 31:
+            raise RuntimeError(f"cat_channels: the result {tuple(a.shape[:-1]) + (C1 + C2,)} has 2^31 elements or more (the kernels' limit)")
+        out = torch.empty(tuple(a.shape[:-1]) + (C1 + C2,), dtype=torch.float32, device=a.device)
+        with _Guard(a, f"cat_channels_fwd[{C1}+{C2}]", 0.0, 8.0 * out.numel()):
+            _call(_L().modet_cat_channels2_fwd, _p(a), _p(b), _p(out), N, C1, C2, _stream())
+        ctx.dims = (N, C1, C2, tuple(a.shape), tuple(b.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        N, C1, C2, sa, sb = ctx.dims
+        dout = dout.contiguous()
+        da = torch.empty(sa, dtype=torch.float32, device=dout.device) if ctx.needs_input_grad[0] else None
+        db = torch.empty(sb, dtype=torch.float32, device=dout.device) if ctx.needs_input_grad[1] else None
+        if da is not None or db is not None:
+            with _Guard(dout, f"cat_channels_bwd[{C1}+{C2}]", 0.0, 8.0 * dout.numel()):
+                _call(_L().modet_cat_channels2_bwd, _p(dout), _p(da), _p(db), N, C1, C2, _stream())
+        return da, db
+
+
+def cat_channels(a, b):
+    """torch.cat([a, b], -1) of two channels-last tensors (RDN's Estimator input, "Baseline methods/RDN/models.py":211-214: the
+    reference concatenates along dim 1 of its planar layout); the backward splits the gradient"""
+    return _CatChannels.apply(a, b)
+
+
 def _na_args(op, C, heads, rpb, bf16):
     """head_dim of C channels in ``heads`` heads; rpb holds heads * 27 biases.  The kernels: head_dim 6 (fused), and in fp32 any
     multiple of 8 up to 128 (csrc/na.hip gen_hd_ok)."""

@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m smilecode_amd.train ...
     python -m smilecode_amd.train --synthetic 4 --img-size 64,64,64 --max-epoch 1      # no data needed
     python -m smilecode_amd.train --model im2grid ...      # the Im2Grid baseline ("Baseline methods/Im2Grid/train.py"), its directory name
+    python -m smilecode_amd.train --model rdn --channels 16 --levels 1,1,1,1 [--diff] ...   # the RDN baseline ("Baseline methods/RDN/train.py")
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ import torch
 from . import data, utils
 from .engine import Trainer, poly_lr
 from .losses import REG_TERMS, SIM_TERMS
-from .models import Im2grid, ModeT
+from .models import RDN, Im2grid, ModeT
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
 
@@ -70,7 +71,7 @@ def latest_checkpoint(model_dir):
     return os.path.join(model_dir, files[-1])
 
 
-MODELS = ("modet", "im2grid")       # --model of train.py and infer.py
+MODELS = ("modet", "im2grid", "rdn")       # --model of train.py and infer.py
 
 
 def make_parser():
@@ -107,8 +108,21 @@ def make_parser():
     ap.add_argument("--int-steps", type=int, default=7, help="scaling-and-squaring steps of --diff (the reference's VecInt default)")
     ap.add_argument("--model", choices=MODELS, default="modet",
                     help="the network: ModeT, or the Im2Grid baseline the paper compares it with (positional-encoding projection + "
-                         "coordinate translator per level; fp32, no --diff, no --overlap-allreduce)")
+                         "coordinate translator per level; fp32, no --diff, no --overlap-allreduce), or the RDN baseline (stride-2 "
+                         "encoder, one Estimator per level; fp32, one stage, --diff = its RDN_diff form, no --overlap-allreduce)")
+    ap.add_argument("--channels", type=int, default=16, help="--model rdn: channels of the first encoder layer (the reference's default)")
+    ap.add_argument("--levels", default="1,1,1,1",
+                    help="--model rdn: Estimator passes per level a,b,c,d, finest level first (the reference's level_recursion)")
     return ap
+
+
+def rdn_levels(args):
+    """--levels as the four pass counts, or None when it is not four positive integers"""
+    try:
+        lv = [int(v) for v in str(getattr(args, "levels", "1,1,1,1")).split(",")]
+    except ValueError:
+        return None
+    return lv if len(lv) == 4 and min(lv) >= 1 else None
 
 
 def check_model_args(ap, args):
@@ -118,12 +132,19 @@ def check_model_args(ap, args):
             ap.error("--diff is ModeT's: the Im2Grid baseline composes its fields without integration")
         if getattr(args, "overlap_allreduce", False):
             ap.error("--overlap-allreduce is ModeT's: the three-stage bucket cut follows ModeT's layers")
+    if args.model == "rdn":
+        if getattr(args, "overlap_allreduce", False):
+            ap.error("--overlap-allreduce is ModeT's: the three-stage bucket cut follows ModeT's layers")
+        if rdn_levels(args) is None:
+            ap.error("--levels takes four positive pass counts a,b,c,d (finest level first), got {!r}".format(args.levels))
     return args
 
 
 def make_model(args, img_size):
     if args.model == "im2grid":
         return Im2grid(img_size)
+    if args.model == "rdn":
+        return RDN(img_size, channels=args.channels, level_recursion=rdn_levels(args), diff=args.diff, int_steps=args.int_steps)
     return ModeT(img_size, head_dim=6, num_heads=[8, 4, 2, 1, 1], scale=1, diff=args.diff, int_steps=args.int_steps)
 
 
@@ -134,6 +155,8 @@ def save_dir_name(args, num_heads, head_dim, weights):
     if getattr(args, "model", "modet") == "im2grid":        # the reference's "Baseline methods/Im2Grid/train.py":49, the terms named alike
         return "Im2Grid_{}_{}_reg_{}{}_lr_{}_54r/".format(args.sim, weights[0], reg, weights[1], args.lr)
     diff = "_diff{}".format(args.int_steps) if getattr(args, "diff", False) else ""
+    if getattr(args, "model", "modet") == "rdn":            # "Baseline methods/RDN/train.py":51 (its "diffusion" is the regulariser's weight)
+        return "RDN({}, {}{}{}{})_{}_{}_diffusion_{}{}_lr_{}{}/".format(1, *rdn_levels(args), args.sim, weights[0], reg, weights[1], args.lr, diff)
     return "modet-heads({}{}{}{}{})-rpe_headim_{}_{}_{}_reg_{}{}_lr_{}_54r{}/".format(*num_heads, head_dim, args.sim, weights[0], reg,
                                                                                      weights[1], args.lr, diff)
 
