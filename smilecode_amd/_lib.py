@@ -195,6 +195,12 @@ FAMILIES = {
         "modet_cat_channels2_fwd": (I, [P, P, P, I64, I, I, P]),
         "modet_cat_channels2_bwd": (I, [P, P, P, I64, I, I, P]),
     }),
+    "deconv": (_header("modet_hip_deconv.h"), {
+        "modet_deconv4s2_ws_bytes": (SZ, [I, I, I, I, I, I, I]),
+        "modet_deconv4s2_fwd": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, I, F, P]),
+        "modet_deconv4s2_bwd_data": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, I, F, P]),
+        "modet_deconv4s2_bwd_weight": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, I, I, F, P]),
+    }),
 }
 # The names a family's entry had before the registry.  Nothing in this tree uses them; they stay because the previous revision's
 # test files, which every change is also run against, reach the library through them (about 95 test ids).  Views of FAMILIES:

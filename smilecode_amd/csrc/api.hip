@@ -3,7 +3,7 @@
 
 extern "C" {
 
-int modet_hip_version(void) { return 446;
+int modet_hip_version(void) { return 447;
   /* 0.4.0: + modet_conv3d_kernel_family_v, conv kernel family 4 (conv_wgrad_tr_kernel); no environment reads in product builds
      0.4.1: + typed (fp32 | bf16) entry points modet_na_{fwd,bwd}_t, modet_proj_ln_*_t, modet_warp_*_t, modet_warp_fwd_o16,
               modet_avgpool2_fwd_x16, modet_instnorm_*_pool_bf16; modet_ncc_*_box (any window); conv kernel family 5 (conv_q_kernel)
@@ -37,7 +37,10 @@ int modet_hip_version(void) { return 446;
      0.4.4.6: + modet_convs2_ws_bytes, modet_convs2_fwd, modet_convs2_bwd_data, modet_convs2_bwd_weight, modet_cat_channels2_fwd,
               modet_cat_channels2_bwd (include/modet_hip_convs2.h): the 3x3x3 convolution with stride 2 and a fused LeakyReLU(slope)
               of the RDN / PCNet / PR++ encoders (fp32 on any input range; gather data gradient, weight gradient by partial rows and
-              one fixed-order fp64 column sum) and the two-tensor channel concatenation */ }
+              one fixed-order fp64 column sum) and the two-tensor channel concatenation
+     0.4.4.7: + modet_deconv4s2_ws_bytes, modet_deconv4s2_fwd, modet_deconv4s2_bwd_data, modet_deconv4s2_bwd_weight
+              (include/modet_hip_deconv.h): the 4x4x4 transposed convolution with stride 2 and padding 1 and a fused
+              LeakyReLU(slope) of the RCN / VTN and PCNet decoders, any channel count up to 1024, on LDS-staged 3-D tiles */ }
 
 const char* modet_hip_strerror(int code) {
   switch (code) {

@@ -67,10 +67,25 @@ class Trainer:
             from .parallel import MODET_BUCKETS, BucketedAllReduce
             self.buckets = BucketedAllReduce(self.fp, list(model.named_parameters()), MODET_BUCKETS, group)
 
+    def _reg_fields(self, outs):
+        """the model outputs the regulariser applies to: output [1], or -- a model that says ``reg_on_subflows`` (RCN, whose
+        reference loss, "Baseline methods/RCN/train.py":106-130, regularises every cascade's subflow and not the composed flow)
+        -- every output [2:], each term weighted by ``weights[1]``"""
+        if not getattr(self.model, "reg_on_subflows", False):
+            _, flow = outs
+            return [flow]
+        if len(outs) < 3:
+            raise RuntimeError(f"Trainer: {type(self.model).__name__} regularises its subflows (outputs [2:]): build it with "
+                               f"return_subflows=True")
+        return list(outs[2:])
+
     def loss(self, moving, fixed):
-        y_moved, flow = self.model(moving, fixed)
+        outs = self.model(moving, fixed)
+        y_moved, fields = outs[0], self._reg_fields(outs)
         sim = self.sim(fixed, y_moved)
-        reg = self.reg(flow, fixed)
+        reg = self.reg(fields[0], fixed)
+        for f in fields[1:]:
+            reg = reg + self.reg(f, fixed)
         if self.weights[0] != 1.0:          # train.py:127-129 multiplies by weights [1, 1]: x * 1.0 == x, and each scalar
             sim = sim * self.weights[0]     # multiplication is a 4 us launch forward and another one backward
         if self.weights[1] != 1.0:
@@ -94,16 +109,22 @@ class Trainer:
         flow (reference losses.py:11-13 indexes (B,3,D,H,W); the kernel reads the channels-last flow the last composition
         wrote) and the copy of its gradient back, the two d * 1.0 passes, autograd's ``ones_like`` root.  Same arithmetic
         element for element: gradients bit-identical to ``loss(...)[0].backward()`` up to the warp scatter's atomic order."""
-        y_cl, flow_cl = self.model.forward_cl(moving, fixed)
+        outs = self.model.forward_cl(moving, fixed)
+        y_cl, fields = outs[0], self._reg_fields(outs)
         B, D, H, W, _ = y_cl.shape
         w0, w1 = float(self.weights[0]), float(self.weights[1])
         sim, d_y = self.sim.value_and_grad(fixed.contiguous(), y_cl.detach().reshape(B, 1, D, H, W), w0)
-        reg, d_flow = self.reg.value_and_grad_cl(flow_cl.detach(), w1)
+        reg, d_flow = self.reg.value_and_grad_cl(fields[0].detach(), w1)
+        d_fields = [d_flow]
+        for f in fields[1:]:                    # (a model with reg_on_subflows: one root and one seed per subflow)
+            r, d = self.reg.value_and_grad_cl(f.detach(), w1)
+            reg = reg + r
+            d_fields.append(d)
         if w0 != 1.0:
             sim = sim * w0
         if w1 != 1.0:
             reg = reg * w1
-        return (sim + reg, sim, reg), [y_cl, flow_cl], [d_y.reshape(y_cl.shape), d_flow]
+        return (sim + reg, sim, reg), [y_cl] + fields, [d_y.reshape(y_cl.shape)] + d_fields
 
     # ---------------------------------------------------------------- hipGraph replay of forward + backward
     def _fwd_bwd(self, moving, fixed):

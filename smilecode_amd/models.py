@@ -16,7 +16,9 @@ state_dict compatibility:
 
 ``Im2grid`` (the baseline of "Baseline methods/Im2Grid/models.py", further down) is built from the same launches plus the
 fused ``PositionalEncodingLayer``, with the same state_dict rules.  ``RDN`` (the baseline of "Baseline methods/RDN/models.py", at
-the end) adds the stride-2 encoder convolution (``ops.conv3d_s2``) and the Estimator on the stride-1 convolutions.
+the end) adds the stride-2 encoder convolution (``ops.conv3d_s2``) and the Estimator on the stride-1 convolutions.  ``VTN`` / ``RCN``
+(the baseline of "Baseline methods/RCN/models.py", after it) add the stride-2 4x4x4 transposed convolution
+(``ops.conv_transpose3d_k4s2``) of the decoder.
 """
 from __future__ import annotations
 
@@ -935,6 +937,257 @@ class RDN(nn.Module):
         if stage_flows:
             return y_moved, flow_out, (sv if self.diff else sflow)
         return y_moved, flow_out
+
+
+class _ConvTranspose3dParams(nn.Module):
+    """parameter holder with nn.ConvTranspose3d's names, shapes and default init for kernel 4: weight (Cin,Cout,4,4,4), whose
+    fan-in torch takes from weight.size(1) (= Cout) times the 64 taps; bias (Cout) or none."""
+
+    def __init__(self, cin, cout, bias=True):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cin, cout, 4, 4, 4))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(cout))
+            bound = 1.0 / math.sqrt(cout * 64)
+            nn.init.uniform_(self.bias, -bound, bound)
+        else:
+            self.register_parameter("bias", None)
+
+
+def _k4s2_only(cls, kernel_size, stride):
+    if kernel_size != 4 or stride != 2:
+        raise RuntimeError(f"{cls}: kernel_size = {kernel_size}, stride = {stride}: the transposed-convolution kernels are built "
+                           f"for kernel 4 and stride 2 only")
+
+
+class UpConvBlock(nn.Module):
+    """nn.ConvTranspose3d(cin, cout, 4, stride=2, bias=False) and the crop [1:-1] of every axis ("Baseline methods/RCN/models.py"
+    UpConvBlock) -- the same function as padding=1, one fused kernel (ops.conv_transpose3d_k4s2); channels-last in/out.
+    ``final``: the weight starts as Normal(0, 1e-5), the flow head."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=4, stride=2, final=False):
+        super().__init__()
+        _k4s2_only("UpConvBlock", kernel_size, stride)
+        self.upconv = _ConvTranspose3dParams(in_channels, out_channels, bias=False)
+        if final:
+            with torch.no_grad():
+                self.upconv.weight.normal_(0.0, 1e-5)
+
+    def forward(self, x, scale=1.0):
+        """``scale``: the result times a constant, folded into the (small) weight; exact for a power of two"""
+        w = self.upconv.weight if scale == 1.0 else self.upconv.weight * float(scale)
+        return ops.conv_transpose3d_k4s2(x, w, None, None)
+
+
+class UpConvLeakyReLU(nn.Module):
+    """nn.ConvTranspose3d(cin, cout, 4, stride=2) with bias, the crop [1:-1] of every axis and LeakyReLU(alpha) ("Baseline
+    methods/RCN/models.py" UpConvLeakyReLU); one fused kernel, channels-last in/out."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=4, stride=2, alpha=0.1):
+        super().__init__()
+        _k4s2_only("UpConvLeakyReLU", kernel_size, stride)
+        self.upconv = _ConvTranspose3dParams(in_channels, out_channels, bias=True)
+        self.alpha = float(alpha)
+
+    def forward(self, x):
+        return ops.conv_transpose3d_k4s2(x, self.upconv.weight, self.upconv.bias, self.alpha)
+
+
+class EncoderS2x6(nn.Module):
+    """VTN's six-level encoder ("Baseline methods/RCN/models.py" Encoder): conv1, conv2 one stride-2 ConvBlock each, conv3 .. conv6 a
+    stride-2 ConvBlock and a stride-1 ConvBlock, LeakyReLU(0.1) throughout; c, 2c, 4c, 8c, 16c, 32c channels at 1/2 .. 1/64.
+
+    The first layer has 2 input channels, which the stride-2 kernels refuse (1 or a multiple of 4).  It runs on 4: the caller
+    hands [moving; fixed; 0; 0], and the (c,2,3,3,3) weight is padded to (c,4,3,3,3) by one row concatenation over its flattened
+    (Cin * 27) axis, whose backward returns exactly the real weight's gradient."""
+
+    def __init__(self, in_channel=2, first_out_channel=16):
+        super().__init__()
+        c = first_out_channel
+        self.conv1 = ConvBlockS2(in_channel, c, alpha=0.1)
+        self.conv2 = ConvBlockS2(c, 2 * c, alpha=0.1)
+        for i, k in zip((3, 4, 5, 6), (2, 4, 8, 16)):
+            setattr(self, "conv%d" % i, nn.Sequential(ConvBlockS2(k * c, 2 * k * c, alpha=0.1), ConvBlock(2 * k * c, 2 * k * c)))
+        self.register_buffer("_wpad", torch.zeros(c, 27 * (4 - in_channel)), persistent=False)
+
+    def forward(self, x4):
+        m = self.conv1.main
+        c = m.weight.shape[0]
+        w4 = ops.cat_channels(m.weight.view(c, -1), self._wpad).view(c, 4, 3, 3, 3)
+        out1 = ops.conv3d_s2(x4, w4, m.bias, self.conv1.alpha)
+        out2 = self.conv2(out1)
+        out3 = self.conv3(out2)
+        out4 = self.conv4(out3)
+        out5 = self.conv5(out4)
+        out6 = self.conv6(out5)
+        return [out1, out2, out3, out4, out5, out6]
+
+
+RCN_MAX_CHANNELS = 8        # 32 x channels <= 256: the widest stride-2 layer (16c -> 32c) and stride-1 layer (32c -> 32c) of the encoder
+RCN_MAX_STRIDE1_WIDTH = 256  # csrc/conv3d.hip: the stride-1 kernels and their data gradient take up to 256 channels on either side
+
+
+def rcn_unsupported_config(in_channel=2, channels=16):
+    """None if every kernel on VTN's path accepts the channel counts, else a message naming the argument (the library is asked for
+    the stride-2 layers; the stride-1 limit is restated, as rdn_unsupported_config does)"""
+    if isinstance(channels, bool) or int(channels) != channels or channels < 1:
+        return f"channels = {channels}: a positive integer (4 or {RCN_MAX_CHANNELS})"
+    if in_channel != 2:
+        return (f"in_channel = {in_channel}: VTN convolves the concatenation [moving; fixed] of two one-channel volumes; only "
+                f"in_channel = 2 is built")
+    L = ops._L()
+    c = channels
+    for cin, cout in [(4, c), (c, 2 * c), (2 * c, 4 * c), (4 * c, 8 * c), (8 * c, 16 * c), (16 * c, 32 * c)]:
+        if L.modet_convs2_ws_bytes(1, 64, 64, 64, cin, cout, 0) == 0:
+            return (f"channels = {channels}: the encoder's stride-2 layer {cin} -> {cout} is refused (the convs2 kernels take 1 or a "
+                    f"multiple of 4 input channels and a multiple of 4 output channels, up to {ops.CONVS2_MAX_CHANNELS}; "
+                    f"channels is 4 or {RCN_MAX_CHANNELS}" + (", the reference's default of 16 is not built)" if channels == 16 else ")"))
+    if 32 * c + 3 > RCN_MAX_STRIDE1_WIDTH + 3 or 32 * c > RCN_MAX_STRIDE1_WIDTH:
+        return (f"channels = {channels}: conv6 convolves {32 * c} -> {32 * c} channels; the stride-1 kernels take up to "
+                f"{RCN_MAX_STRIDE1_WIDTH}")
+    return None
+
+
+def rcn_unsupported_shape(shape):
+    """None, or why a (D,H,W) volume cannot go through VTN's six levels"""
+    shape = tuple(shape)
+    if len(shape) != 3:
+        return f"(D, H, W) expected, got {shape}"
+    if any(int(v) < 64 or int(v) % 64 != 0 for v in shape):
+        return (f"every spatial dimension must be a multiple of 64, got {shape}: six stride-2 layers halve it rounding up and the "
+                f"transposed convolutions double it back, so at any other size the skip concatenations meet different grids -- the "
+                f"reference itself raises in torch.cat at its own (160, 192, 160), where level 5 is 5x6x5 from the encoder and "
+                f"6x6x6 from Deconv5")
+    return None
+
+
+class VTN(nn.Module):
+    """The VTN network of the RCN baseline ("Baseline methods/RCN/models.py" VTN): a six-level stride-2 encoder over [moving; fixed],
+    and a decoder that predicts a 3-channel flow per level (Pred6 .. Pred2, stride-1 convolutions), upsamples it (Upsamp*) and the
+    features (Deconv*) by stride-2 4x4x4 transposed convolutions and concatenates [skip; deconv; flow]; Pred0 is the last upsampling.
+    Same constructor arguments, attribute names and state-dict keys as the reference (``transformer.grid`` as ModeT handles it).
+    ``forward(moving, fixed)`` returns ``(y_moved, flow)`` with ``warp=True`` and ``flow`` without.  fp32 only."""
+
+    stage_buckets = False
+
+    def __init__(self, inshape=(160, 192, 160), flow_multiplier=1., in_channel=2, channels=16, warp=True, legacy_grid_buffers=False,
+                 act_dtype=torch.float32):
+        super().__init__()
+        name = type(self).__name__
+        if act_dtype != torch.float32:
+            raise RuntimeError(f"{name}: act_dtype = {act_dtype}: the stride-2 and transposed convolution kernels are fp32 only (bf16 "
+                               f"storage is ModeT's)")
+        why = rcn_unsupported_config(in_channel, channels)
+        if why is not None:
+            raise RuntimeError(f"{name}: " + why)
+        why = rcn_unsupported_shape(inshape)
+        if why is not None:
+            raise RuntimeError(f"{name}: inshape: " + why)
+        self.flow_multiplier = flow_multiplier
+        self.channels = channels
+        self.step = 7
+        self.inshape = tuple(int(s) for s in inshape)
+        self.warp = warp
+        self.act_dtype = act_dtype
+        dims, c = 3, channels
+        self.encoder = EncoderS2x6(in_channel=in_channel, first_out_channel=c)
+        self.Pred6 = _Conv3dParams(32 * c, dims)
+        self.Upsamp6to5 = UpConvBlock(dims, dims, 4, 2)
+        self.Deconv5 = UpConvLeakyReLU(32 * c, 16 * c, 4, 2)
+        for lvl, k in ((5, 16), (4, 8), (3, 4), (2, 2)):
+            cin = 2 * k * c + dims
+            setattr(self, "Pred%d" % lvl, _Conv3dParams(cin, dims))
+            setattr(self, "Upsamp%dto%d" % (lvl, lvl - 1), UpConvBlock(dims, dims, 4, 2))
+            setattr(self, "Deconv%d" % (lvl - 1), UpConvLeakyReLU(cin, k * c // 2, 4, 2))
+        self.Pred0 = UpConvBlock(c + c + dims, dims, 4, 2, final=True)
+        if warp:
+            self.transformer = SpatialTransformer(self.inshape, legacy_grid_buffers=legacy_grid_buffers)
+
+    def flow_cl(self, mov_cl, fix_cl):
+        """the flow (B,D,H,W,3) of two channels-last one-channel volumes"""
+        x4 = ops.cat_channels(ops.cat_channels(mov_cl, fix_cl), mov_cl.new_zeros(tuple(mov_cl.shape[:-1]) + (2,)))
+        with ops.trace_range("encoder"):
+            feats = self.encoder(x4)
+        with ops.trace_range("decoder"):
+            w = ops.conv3d(feats[5], self.Pred6.weight, self.Pred6.bias, False)
+            w = self.Upsamp6to5(w)
+            cat = ops.cat_channels(ops.cat_channels(feats[4], self.Deconv5(feats[5])), w)
+            for lvl in (5, 4, 3, 2):
+                pred = getattr(self, "Pred%d" % lvl)
+                w = ops.conv3d(cat, pred.weight, pred.bias, False)
+                w = getattr(self, "Upsamp%dto%d" % (lvl, lvl - 1))(w)
+                cat = ops.cat_channels(ops.cat_channels(feats[lvl - 2], getattr(self, "Deconv%d" % (lvl - 1))(cat)), w)
+            return self.Pred0(cat, self.flow_multiplier)
+
+    def _volumes(self, moving, fixed):
+        name = type(self).__name__
+        if moving.shape != fixed.shape or moving.dim() != 5 or moving.shape[1] != 1:
+            raise RuntimeError(f"{name}.forward expects two (B,1,D,H,W) volumes of the same shape")
+        why = rcn_unsupported_shape(moving.shape[2:])
+        if why is not None:
+            raise RuntimeError(f"{name}.forward: " + why)
+        return ops.to_channels_last(moving.contiguous()), ops.to_channels_last(fixed.contiguous())
+
+    def forward_cl(self, moving, fixed):
+        """``forward`` with the results channels-last, as the kernels wrote them"""
+        mov_cl, fix_cl = self._volumes(moving, fixed)
+        flow = self.flow_cl(mov_cl, fix_cl)
+        if not self.warp:
+            return flow
+        return ops.warp_tee(mov_cl, flow)
+
+    def forward(self, moving, fixed):
+        out = self.forward_cl(moving, fixed)
+        return tuple(ops.to_ncdhw(t) for t in out) if self.warp else ops.to_ncdhw(out)
+
+
+class RCN(nn.Module):
+    """The recursive cascade of the RCN baseline ("Baseline methods/RCN/models.py" RCN / RCN_test): ``n_cascade`` VTNs, each fed the
+    moving image warped by the flow composed so far, ``flow = ST(flow, w) + w``.  Same constructor arguments, attribute names and
+    state-dict keys as the reference (``vtn.<i>.*``).  ``forward(moving, fixed)`` returns ``(moved, flow)`` -- RCN_test -- and with
+    ``return_subflows=True`` the reference's training tuple ``(moved, flow, *subflows)`` -- RCN.  fp32 only."""
+
+    stage_buckets = False       # engine.Trainer: the three-stage bucket cut of the overlapped all-reduce is ModeT's
+    reg_on_subflows = True      # engine.Trainer: the regulariser applies to every output [2:] (the subflows), not to output [1]
+
+    def __init__(self, inshape=(160, 192, 160), flow_multiplier=1., in_channel=2, channels=16, n_cascade=10, return_subflows=False,
+                 legacy_grid_buffers=False, act_dtype=torch.float32):
+        super().__init__()
+        if isinstance(n_cascade, bool) or not isinstance(n_cascade, int) or n_cascade < 1:
+            raise RuntimeError(f"RCN: n_cascade = {n_cascade!r}: a positive integer")
+        try:
+            self.vtn = nn.ModuleList([VTN(inshape=inshape, flow_multiplier=flow_multiplier, in_channel=in_channel, channels=channels,
+                                          warp=False, act_dtype=act_dtype) for _ in range(n_cascade)])
+        except RuntimeError as e:
+            raise RuntimeError("RCN" + str(e)[len("VTN"):]) from None
+        self.n = n_cascade
+        self.channels = channels
+        self.inshape = self.vtn[0].inshape
+        self.return_subflows = bool(return_subflows)
+        self.act_dtype = act_dtype
+        self.transformer = SpatialTransformer(self.inshape, legacy_grid_buffers=legacy_grid_buffers)
+
+    def forward(self, moving, fixed):
+        return tuple(ops.to_ncdhw(t) for t in self._run(moving, fixed, self.return_subflows))
+
+    def forward_cl(self, moving, fixed):
+        """``forward`` with the results channels-last, as the kernels wrote them: moved (B,D,H,W,1), flow and subflows (B,D,H,W,3)"""
+        return self._run(moving, fixed, self.return_subflows)
+
+    def _run(self, moving, fixed, subflows):
+        try:
+            mov_cl, fix_cl = self.vtn[0]._volumes(moving, fixed)
+        except RuntimeError as e:
+            raise RuntimeError("RCN" + str(e)[len("VTN"):]) from None
+        flow, moved, subs = None, mov_cl, []
+        for i in range(self.n):
+            with ops.trace_range("cascade%d" % i):
+                w = self.vtn[i].flow_cl(moved, fix_cl)
+                subs.append(w)
+                flow = w if i == 0 else self.transformer.forward_cl(flow, w, add_flow=True)
+                moved, flow = ops.warp_tee(mov_cl, flow)        # (the flow's other consumer: the next composition, or the caller)
+        return (moved, flow, *subs) if subflows else (moved, flow)
 
 
 def load_numpy_weights(model: nn.Module, weights) -> None:

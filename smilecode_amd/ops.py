@@ -1411,6 +1411,93 @@ def cat_channels(a, b):
     return _CatChannels.apply(a, b)
 
 
+DECONV_MAX_CHANNELS = 1024       # MODET_DECONV_MAX_CHANNELS of include/modet_hip_deconv.h
+
+
+def conv_transpose3d_k4s2_out_shape(D, H, W):
+    """the output grid of a 4x4x4 transposed convolution with stride 2 and padding 1: 2 n per axis"""
+    return tuple(2 * int(n) for n in (D, H, W))
+
+
+def _deconv_args(op, x, w, b, slope):
+    """x (B,D,H,W,Cin); w (Cin,Cout,4,4,4); b (Cout,) or None; slope None or a float >= 0 -> (B, D, H, W, Cin, Cout, act, slope)"""
+    if getattr(x, "data16", None) is not None:
+        raise RuntimeError(f"{op}: x is a bf16 feature handle; the transposed-convolution kernels are fp32 only")
+    _chk(x, w, b)
+    _rank5(op, "x", x)
+    if w.dim() != 5:
+        raise RuntimeError(f"{op}: weight must be (Cin,Cout,4,4,4), got {tuple(w.shape)}")
+    B, D, H, W, Cin = x.shape
+    Cout = w.shape[1]
+    _same_shape(op, "weight", w, (Cin, Cout, 4, 4, 4), f"x {tuple(x.shape)}")
+    _same_shape(op, "bias", b, (Cout,), f"weight {tuple(w.shape)}")
+    if slope is not None and not (isinstance(slope, (int, float)) and not isinstance(slope, bool) and slope >= 0.0):
+        raise RuntimeError(f"{op}: slope must be None (no activation) or a number >= 0 (0.0: ReLU), got {slope!r}")
+    if min(B, D, H, W, Cin, Cout) < 1:
+        raise RuntimeError(f"{op}: x {tuple(x.shape)} or weight {tuple(w.shape)} is empty")
+    if Cin > DECONV_MAX_CHANNELS:
+        raise RuntimeError(f"{op}: x has {Cin} channels: the kernels take 1 to {DECONV_MAX_CHANNELS}")
+    if Cout > DECONV_MAX_CHANNELS:
+        raise RuntimeError(f"{op}: weight has {Cout} output channels: the kernels take 1 to {DECONV_MAX_CHANNELS}")
+    if _L().modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, 0) == 0:
+        raise RuntimeError(f"{op}: x {tuple(x.shape)} -> {Cout} channels: a tensor of 2^31 elements or more (the kernels' limit)")
+    return B, D, H, W, Cin, Cout, int(slope is not None), float(slope or 0.0)
+
+
+class _ConvTranspose3dK4S2(Function):
+    """nn.ConvTranspose3d(Cin, Cout, 4, stride=2, padding=1) [+ LeakyReLU(slope)] on channels-last voxels; the backward folds the
+    activation's derivative into its d_y loads and skips the data gradient of an input that needs none."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, slope):
+        B, D, H, W, Cin, Cout, act, sl = _deconv_args("conv_transpose3d_k4s2", x, w, b, slope)
+        L = _L()
+        y = torch.empty((B, 2 * D, 2 * H, 2 * W, Cout), dtype=torch.float32, device=x.device)
+        nb = L.modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, 0)
+        ws = _ws(nb, x)
+        with _Guard(x, f"deconv_fwd[{Cin}->{Cout}]", 128.0 * Cin * Cout * B * D * H * W,4.0 * (x.numel() + y.numel())):
+            _call(L.modet_deconv4s2_fwd, _p(x), _p(w), _p(b), _p(y), _p(ws), nb, B, D, H, W, Cin, Cout, act, sl, _stream())
+        ctx.save_for_backward(x, w, b, y if act else None)
+        ctx.act, ctx.slope, ctx.step = act, sl, current_step()
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b, y = ctx.saved_tensors
+        B, D, H, W, Cin = x.shape
+        Cout, L = w.shape[1], _L()
+        dy = dy.contiguous()
+        dims = (B, D, H, W, Cin, Cout, ctx.act, ctx.slope)
+        flops = 128.0 * Cin * Cout * (x.numel() // Cin)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            nb = L.modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, 1)
+            ws = _ws(nb, x)
+            with _Guard(x, f"deconv_bwd_data[{Cout}->{Cin}]", flops, 4.0 * (x.numel() + (1 + ctx.act) * dy.numel())):
+                _call(L.modet_deconv4s2_bwd_data, _p(dy), _p(y), _p(w), _p(dx), _p(ws), nb, *dims, _stream())
+        ret = [None, None]
+        if ctx.needs_input_grad[1] or (b is not None and ctx.needs_input_grad[2]):
+            # written straight into the step's gradient buffer where the scope hands out destinations; the launch reduces its own
+            # partial rows, as the stride-2 convolution's (DESIGN.md 4.11, 4.12)
+            params = (w,) if b is None else (w, b)
+            dsts, _, back = _param_dsts(ctx.step, *params)
+            ret = list(back) + [None] * (2 - len(back))
+            nb = L.modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, 2)
+            ws = _ws(nb, x)
+            with _Guard(x, f"deconv_bwd_weight[{Cin}->{Cout}]", flops, 4.0 * (x.numel() + (1 + ctx.act) * dy.numel())):
+                _call(L.modet_deconv4s2_bwd_weight, _p(x), _p(dy), _p(y), _p(dsts[0]), _p(dsts[1] if b is not None else None), _p(ws),
+                      nb, *dims, _stream())
+        return (dx, ret[0], ret[1], None)
+
+
+def conv_transpose3d_k4s2(x, w, b=None, slope=None):
+    """4x4x4 transposed convolution with stride 2 and padding 1 on channels-last voxels, then LeakyReLU(slope) (slope=None: no
+    activation, 0.0: ReLU) -- the upsampling layer of the RCN / VTN decoder ("Baseline methods/RCN/models.py": ConvTranspose3d(4,
+    stride=2) and the crop [1:-1] of every axis, the same function).  x (B,D,H,W,Cin), w (Cin,Cout,4,4,4) -> (B,2D,2H,2W,Cout)."""
+    return _ConvTranspose3dK4S2.apply(x, w, b, slope)
+
+
 def _na_args(op, C, heads, rpb, bf16):
     """head_dim of C channels in ``heads`` heads; rpb holds heads * 27 biases.  The kernels: head_dim 6 (fused), and in fp32 any
     multiple of 8 up to 128 (csrc/na.hip gen_hd_ok)."""
