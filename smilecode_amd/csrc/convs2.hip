@@ -7,50 +7,15 @@
 // launch without a grid cap: one thread per (output voxel, 4 output channels) in the forward, per (input voxel, 4 input channels)
 // in the data gradient, per (tap, 4 ci, 4 co) item and voxel split in the weight gradient.  The weights are re-laid by a first
 // launch so that the 4 channels a thread owns are one 16-byte load and the lanes of a wave read consecutive vectors.
-#include "common.h"
+#include "strided.h"
 #include "../../include/modet_hip_convs2.h"
 
 namespace {
 
-constexpr int BLK = 256;
 constexpr int MAXC = MODET_CONVS2_MAX_CHANNELS;
+#define FAMILY 27, false, false          // strided.h's T, PAD, CIN_MAJOR: w (Cout,Cin,27), channel counts as they are
 
 struct Dims { int B, D, H, W, Do, Ho, Wo, Cin, Cout; };
-
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 f4fma(float a, float4 b, float4 c) {
-  return make_float4(fmaf(a, b.x, c.x), fmaf(a, b.y, c.y), fmaf(a, b.z, c.z), fmaf(a, b.w, c.w));
-}
-__device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-// d_y split by the sign of y: gp counts with weight 1, gq with weight slope
-__device__ __forceinline__ void split_pq(float g, float yv, float& gp, float& gq) {
-  const bool pos = yv > 0.f;
-  gp = pos ? g : 0.f;
-  gq = pos ? 0.f : g;
-}
-
-// w (Cout,Cin,27) -> [tap][ci][co] (to_dgrad == 0) or [tap][co][ci] (to_dgrad == 1)
-__global__ __launch_bounds__(BLK) void convs2_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int Cin, int Cout,
-                                                          int to_dgrad) {
-  const int n = 27 * Cin * Cout;
-  const int i = blockIdx.x * BLK + threadIdx.x;
-  if (i >= n) return;
-  int tap, ci, co;
-  if (to_dgrad) {
-    ci = i % Cin;
-    const int r = i / Cin;
-    co = r % Cout;
-    tap = r / Cout;
-  } else {
-    co = i % Cout;
-    const int r = i / Cout;
-    ci = r % Cin;
-    tap = r / Cin;
-  }
-  out[i] = w[((int64_t)co * Cin + ci) * 27 + tap];
-}
 
 // thread t = (output voxel, group of 4 output channels); CI = 1 (Cin == 1) or 4 (Cin % 4 == 0)
 template <int CI>
@@ -258,38 +223,6 @@ __global__ __launch_bounds__(BLK) void convs2_bwd_weight_kernel(const float* __r
   }
 }
 
-// Stage 2: thread = column; the rows of all voxel splits in split order, four interleaved fp64 chains, P + slope * Q, one rounding
-template <bool ACT>
-__global__ __launch_bounds__(BLK) void convs2_colsum_kernel(const float* __restrict__ part, int rows, int Cin, int Cout, double slope,
-                                                            float* __restrict__ d_w, float* __restrict__ d_b) {
-  const int64_t R = (int64_t)27 * Cin * Cout + Cout;
-  const int64_t c = (int64_t)blockIdx.x * BLK + threadIdx.x;
-  if (c >= R) return;
-  constexpr int NQ = ACT ? 2 : 1;
-  double res[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    int r = 0;
-    for (; r + 3 < rows; r += 4) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a[u] += (double)part[((int64_t)(r + u) * NQ + q) * R + c];
-    }
-    for (; r < rows; ++r) a[0] += (double)part[((int64_t)r * NQ + q) * R + c];
-    res[q] = (a[0] + a[1]) + (a[2] + a[3]);
-  }
-  const double val = ACT ? fma(slope, res[NQ - 1], res[0]) : res[0];
-  const int64_t nW = R - Cout;
-  if (c < nW) {
-    const int co = (int)(c % Cout);
-    const int64_t r = c / Cout;
-    const int ci = (int)(r % Cin), tap = (int)(r / Cin);
-    d_w[((int64_t)co * Cin + ci) * 27 + tap] = (float)val;
-  } else if (d_b != nullptr) {
-    d_b[c - nW] = (float)val;
-  }
-}
-
 // out[n, :C1] = a[n], out[n, C1:] = b[n]; T = float4 with C1, C2 counted in vectors, or float
 template <typename T>
 __global__ __launch_bounds__(BLK) void cat2_fwd_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out,
@@ -316,8 +249,6 @@ __global__ __launch_bounds__(BLK) void cat2_bwd_kernel(const T* __restrict__ d_o
   }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 inline int split_voxels(int Cout) { return Cout <= 64 ? 256 : Cout <= 128 ? 512 : 1024; }
 inline int out_dim(int n) { return (n - 1) / 2 + 1; }
 
@@ -329,15 +260,9 @@ inline int covered(int B, int D, int H, int W, int Cin, int Cout) {
   if ((int64_t)B * out_dim(D) * out_dim(H) * out_dim(W) * Cout >= lim) return MODET_ERR_DIM;
   return MODET_OK;
 }
-inline int act_ok(int act, float slope) {
-  if (act != 0 && act != 1) return MODET_ERR_UNSUPPORTED;
-  if (act == 1 && !(slope >= 0.f)) return MODET_ERR_UNSUPPORTED;      // (a NaN slope fails the comparison too)
-  return MODET_OK;
-}
 inline Dims dims_of(int B, int D, int H, int W, int Cin, int Cout) {
   return Dims{B, D, H, W, out_dim(D), out_dim(H), out_dim(W), Cin, Cout};
 }
-inline unsigned blocks_for(int64_t n) { return (unsigned)cdiv64(n, (int64_t)BLK); }
 
 }  // namespace
 
@@ -355,16 +280,13 @@ size_t modet_convs2_ws_bytes(int B, int D, int H, int W, int Cin, int Cout, int 
 
 int modet_convs2_fwd(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int B, int D, int H,
                      int W, int Cin, int Cout, int act, float slope, modet_stream_t stream) {
-  MODET_CHECK_PTR(x); MODET_CHECK_PTR(w); MODET_CHECK_PTR(y); MODET_CHECK_PTR(ws);
-  int rc = covered(B, D, H, W, Cin, Cout);
-  if (rc == MODET_OK) rc = act_ok(act, slope);
+  const int rc = check_call(x, y, y, w, bias, ws, ws_bytes, modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, MODET_CONVS2_PASS_FWD),
+                            covered(B, D, H, W, Cin, Cout), Cin, Cout, act, slope);
   if (rc != MODET_OK) return rc;
-  if (!(Cin == 1 ? aligned4(x) : aligned16(x)) || !aligned16(y) || !aligned4(w) || !aligned4(bias)) return MODET_ERR_UNSUPPORTED;
-  if (ws_bytes < modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, MODET_CONVS2_PASS_FWD) || !aligned16(ws)) return MODET_ERR_WORKSPACE;
   const Dims s = dims_of(B, D, H, W, Cin, Cout);
   hipStream_t st = (hipStream_t)stream;
   float* wp = (float*)ws;
-  hipLaunchKernelGGL(convs2_pack_kernel, dim3(blocks_for((int64_t)27 * Cin * Cout)), dim3(BLK), 0, st, w, wp, Cin, Cout, 0);
+  launch_pack<FAMILY>(w, wp, Cin, Cout, 0, st);
   const int64_t total = (int64_t)B * s.Do * s.Ho * s.Wo * (Cout / 4);
   if (Cin == 1)
     hipLaunchKernelGGL(convs2_fwd_kernel<1>, dim3(blocks_for(total)), dim3(BLK), 0, st, x, (const float*)wp, bias, y, s, total, act, slope);
@@ -375,18 +297,13 @@ int modet_convs2_fwd(const float* x, const float* w, const float* bias, float* y
 
 int modet_convs2_bwd_data(const float* d_y, const float* y, const float* w, float* d_x, void* ws, size_t ws_bytes, int B, int D,
                           int H, int W, int Cin, int Cout, int act, float slope, modet_stream_t stream) {
-  MODET_CHECK_PTR(d_y); MODET_CHECK_PTR(w); MODET_CHECK_PTR(d_x); MODET_CHECK_PTR(ws);
-  int rc = covered(B, D, H, W, Cin, Cout);
-  if (rc == MODET_OK) rc = act_ok(act, slope);
+  const int rc = check_call(d_x, d_y, y, w, nullptr, ws, ws_bytes, modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, MODET_CONVS2_PASS_BWD_DATA),
+                            covered(B, D, H, W, Cin, Cout), Cin, Cout, act, slope);
   if (rc != MODET_OK) return rc;
-  if (act == 1) MODET_CHECK_PTR(y);
-  if (!(Cin == 1 ? aligned4(d_x) : aligned16(d_x)) || !aligned16(d_y) || (act == 1 && !aligned16(y)) || !aligned4(w))
-    return MODET_ERR_UNSUPPORTED;
-  if (ws_bytes < modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, MODET_CONVS2_PASS_BWD_DATA) || !aligned16(ws)) return MODET_ERR_WORKSPACE;
   const Dims s = dims_of(B, D, H, W, Cin, Cout);
   hipStream_t st = (hipStream_t)stream;
   float* wd = (float*)ws;
-  hipLaunchKernelGGL(convs2_pack_kernel, dim3(blocks_for((int64_t)27 * Cin * Cout)), dim3(BLK), 0, st, w, wd, Cin, Cout, 1);
+  launch_pack<FAMILY>(w, wd, Cin, Cout, 1, st);
   const int64_t total = (int64_t)B * D * H * W * (Cin == 1 ? 1 : Cin / 4);
   const dim3 grid(blocks_for(total));
 #define LAUNCH_BD(CI_, ACT_) \
@@ -399,14 +316,9 @@ int modet_convs2_bwd_data(const float* d_y, const float* y, const float* w, floa
 
 int modet_convs2_bwd_weight(const float* x, const float* d_y, const float* y, float* d_w, float* d_b, void* ws, size_t ws_bytes,
                             int B, int D, int H, int W, int Cin, int Cout, int act, float slope, modet_stream_t stream) {
-  MODET_CHECK_PTR(x); MODET_CHECK_PTR(d_y); MODET_CHECK_PTR(d_w); MODET_CHECK_PTR(ws);
-  int rc = covered(B, D, H, W, Cin, Cout);
-  if (rc == MODET_OK) rc = act_ok(act, slope);
+  const int rc = check_call(x, d_y, y, d_w, d_b, ws, ws_bytes, modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, MODET_CONVS2_PASS_BWD_WEIGHT),
+                            covered(B, D, H, W, Cin, Cout), Cin, Cout, act, slope);
   if (rc != MODET_OK) return rc;
-  if (act == 1) MODET_CHECK_PTR(y);
-  if (!(Cin == 1 ? aligned4(x) : aligned16(x)) || !aligned16(d_y) || (act == 1 && !aligned16(y)) || !aligned4(d_w) || !aligned4(d_b))
-    return MODET_ERR_UNSUPPORTED;
-  if (ws_bytes < modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, MODET_CONVS2_PASS_BWD_WEIGHT) || !aligned16(ws)) return MODET_ERR_WORKSPACE;
   const Dims s = dims_of(B, D, H, W, Cin, Cout);
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)ws;
@@ -420,11 +332,7 @@ int modet_convs2_bwd_weight(const float* x, const float* d_y, const float* y, fl
   if (Cin == 1) { if (act) LAUNCH_BW(1, true); else LAUNCH_BW(1, false); }
   else { if (act) LAUNCH_BW(4, true); else LAUNCH_BW(4, false); }
 #undef LAUNCH_BW
-  const int64_t R = (int64_t)27 * Cin * Cout + Cout;
-  if (act)
-    hipLaunchKernelGGL(convs2_colsum_kernel<true>, dim3(blocks_for(R)), dim3(BLK), 0, st, (const float*)part, S, Cin, Cout, (double)slope, d_w, d_b);
-  else
-    hipLaunchKernelGGL(convs2_colsum_kernel<false>, dim3(blocks_for(R)), dim3(BLK), 0, st, (const float*)part, S, Cin, Cout, 0.0, d_w, d_b);
+  launch_colsum<FAMILY>(part, S, Cin, Cout, act, slope, d_w, d_b, st);
   return modet_launch_status();
 }
 

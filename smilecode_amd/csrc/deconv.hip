@@ -11,25 +11,18 @@
 // zero-padded to multiples of 4 channels by a first launch, are wave-uniform 16-byte loads.  LDS rows: 16 + 4 floats in the forward
 // (5 16-byte slots: consecutive voxels of a ds_read_b128 lane group fall on different slots), one slot in the gradient, whose
 // lanes are two voxels apart (2-way conflicts: cdna_hip_programming.md's bank rule has no even stride without them).
-#include "common.h"
+#include "strided.h"
 #include "../../include/modet_hip_deconv.h"
 
 namespace {
 
-constexpr int BLK = 256;
+#define FAMILY 64, true, true            // strided.h's T, PAD, CIN_MAJOR: w (Cin,Cout,64), channel counts padded to multiples of 4
 constexpr int MAXC = MODET_DECONV_MAX_CHANNELS;
 constexpr int CK = 16;                   // input channels per staged chunk of the forward
 constexpr int LS4 = CK / 4 + 1;          // LDS row of a window voxel in 16-byte slots (one slot of padding)
 
 struct Dims { int B, D, H, W, Cin, Cout; };
 
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 f4fma(float a, float4 b, float4 c) {
-  return make_float4(fmaf(a, b.x, c.x), fmaf(a, b.y, c.y), fmaf(a, b.z, c.z), fmaf(a, b.w, c.w));
-}
-__device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 // channels [c, c + 4) of a row of C channels: one 16-byte load (VEC: C % 4 == 0) or a scalar tail that stays below C
 template <bool VEC>
 __device__ __forceinline__ float4 ldc4(const float* __restrict__ row, int c, int C) {
@@ -48,39 +41,6 @@ __device__ __forceinline__ void stc4(float* __restrict__ row, int c, int C, floa
   if (c + 1 < C) row[c + 1] = v.y;
   if (c + 2 < C) row[c + 2] = v.z;
   if (c + 3 < C) row[c + 3] = v.w;
-}
-// d_y split by the sign of y: gp counts with weight 1, gq with weight slope
-__device__ __forceinline__ void split_pq(float g, float yv, float& gp, float& gq) {
-  const bool pos = yv > 0.f;
-  gp = pos ? g : 0.f;
-  gq = pos ? 0.f : g;
-}
-__device__ __forceinline__ void split_pq4(float4 g, float4 yv, float4& gp, float4& gq) {
-  split_pq(g.x, yv.x, gp.x, gq.x); split_pq(g.y, yv.y, gp.y, gq.y);
-  split_pq(g.z, yv.z, gp.z, gq.z); split_pq(g.w, yv.w, gp.w, gq.w);
-}
-__host__ __device__ inline int pad4(int c) { return (c + 3) & ~3; }
-
-// w (Cin,Cout,64) -> [tap][ci][co] (to_dgrad == 0) or [tap][co][ci] (to_dgrad == 1), both counts padded to CiP, CoP with zeros
-__global__ __launch_bounds__(BLK) void deconv_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int Cin, int Cout,
-                                                          int to_dgrad) {
-  const int CiP = pad4(Cin), CoP = pad4(Cout);
-  const int n = 64 * CiP * CoP;
-  const int i = blockIdx.x * BLK + threadIdx.x;
-  if (i >= n) return;
-  int tap, ci, co;
-  if (to_dgrad) {
-    ci = i % CiP;
-    const int r = i / CiP;
-    co = r % CoP;
-    tap = r / CoP;
-  } else {
-    co = i % CoP;
-    const int r = i / CoP;
-    ci = r % CiP;
-    tap = r / CiP;
-  }
-  out[i] = (ci < Cin && co < Cout) ? w[((int64_t)ci * Cout + co) * 64 + tap] : 0.f;
 }
 
 // Workgroup = (tile of TD x TH x TW input voxels, 256 / NV groups of 4 output channels); thread = (voxel, group).  Neighbour n in
@@ -326,47 +286,6 @@ __global__ __launch_bounds__(BLK) void deconv_bwd_weight_kernel(const float* __r
   }
 }
 
-// Stage 2: thread = column; the rows of all voxel splits in split order, four interleaved fp64 chains, P + slope * Q, one rounding
-template <bool ACT>
-__global__ __launch_bounds__(BLK) void deconv_colsum_kernel(const float* __restrict__ part, int rows, int Cin, int Cout, double slope,
-                                                            float* __restrict__ d_w, float* __restrict__ d_b) {
-  const int CiP = pad4(Cin), CoP = pad4(Cout);
-  const int64_t R = (int64_t)64 * CiP * CoP + CoP;
-  const int64_t c = (int64_t)blockIdx.x * BLK + threadIdx.x;
-  if (c >= R) return;
-  const int64_t nW = R - CoP;
-  const int co = (int)(c % CoP);
-  int ci = 0, tap = 0;
-  if (c < nW) {
-    const int64_t r = c / CoP;
-    ci = (int)(r % CiP);
-    tap = (int)(r / CiP);
-  } else if (d_b == nullptr) {
-    return;
-  }
-  if (co >= Cout || ci >= Cin) return;                       // a padding column
-  constexpr int NQ = ACT ? 2 : 1;
-  double res[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    int r = 0;
-    for (; r + 3 < rows; r += 4) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a[u] += (double)part[((int64_t)(r + u) * NQ + q) * R + c];
-    }
-    for (; r < rows; ++r) a[0] += (double)part[((int64_t)r * NQ + q) * R + c];
-    res[q] = (a[0] + a[1]) + (a[2] + a[3]);
-  }
-  const double val = ACT ? fma(slope, res[NQ - 1], res[0]) : res[0];
-  if (c < nW) d_w[((int64_t)ci * Cout + co) * 64 + tap] = (float)val;
-  else d_b[co] = (float)val;
-}
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-inline bool aligned_for(const void* p, int C) { return C % 4 == 0 ? aligned16(p) : aligned4(p); }
-
 inline int covered(int B, int D, int H, int W, int Cin, int Cout) {
   if (B < 1 || D < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return MODET_ERR_DIM;
   if (Cin > MAXC || Cout > MAXC) return MODET_ERR_UNSUPPORTED;
@@ -375,12 +294,6 @@ inline int covered(int B, int D, int H, int W, int Cin, int Cout) {
   if (n >= lim || n * Cin >= lim || n * 8 >= lim || n * 8 * Cout >= lim) return MODET_ERR_DIM;
   return MODET_OK;
 }
-inline int act_ok(int act, float slope) {
-  if (act != 0 && act != 1) return MODET_ERR_UNSUPPORTED;
-  if (act == 1 && !(slope >= 0.f)) return MODET_ERR_UNSUPPORTED;      // (a NaN slope fails the comparison too)
-  return MODET_OK;
-}
-inline unsigned blocks_for(int64_t n) { return (unsigned)cdiv64(n, (int64_t)BLK); }
 inline int split_voxels(int64_t N) { const int64_t v = cdiv64(N, 256); return v < 256 ? 256 : (int)v; }
 inline size_t packed_bytes(int Cin, int Cout) { return (size_t)64 * pad4(Cin) * pad4(Cout) * sizeof(float); }
 
@@ -403,16 +316,13 @@ size_t modet_deconv4s2_ws_bytes(int B, int D, int H, int W, int Cin, int Cout, i
 
 int modet_deconv4s2_fwd(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int B, int D, int H,
                         int W, int Cin, int Cout, int act, float slope, modet_stream_t stream) {
-  MODET_CHECK_PTR(x); MODET_CHECK_PTR(w); MODET_CHECK_PTR(y); MODET_CHECK_PTR(ws);
-  int rc = covered(B, D, H, W, Cin, Cout);
-  if (rc == MODET_OK) rc = act_ok(act, slope);
+  const int rc = check_call(x, y, y, w, bias, ws, ws_bytes, modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, MODET_DECONV_PASS_FWD),
+                            covered(B, D, H, W, Cin, Cout), Cin, Cout, act, slope);
   if (rc != MODET_OK) return rc;
-  if (!aligned_for(x, Cin) || !aligned_for(y, Cout) || !aligned4(w) || !aligned4(bias)) return MODET_ERR_UNSUPPORTED;
-  if (ws_bytes < modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, MODET_DECONV_PASS_FWD) || !aligned16(ws)) return MODET_ERR_WORKSPACE;
   const Dims s{B, D, H, W, Cin, Cout};
   hipStream_t st = (hipStream_t)stream;
   float* wp = (float*)ws;
-  hipLaunchKernelGGL(deconv_pack_kernel, dim3(blocks_for((int64_t)64 * pad4(Cin) * pad4(Cout))), dim3(BLK), 0, st, w, wp, Cin, Cout, 0);
+  launch_pack<FAMILY>(w, wp, Cin, Cout, 0, st);
   const int CoG = pad4(Cout) / 4;
   const bool vx = Cin % 4 == 0, vy = Cout % 4 == 0;
 #define LAUNCH_F3(TD_, TH_, TW_, VX_, VY_)                                                                                      \
@@ -439,17 +349,13 @@ int modet_deconv4s2_fwd(const float* x, const float* w, const float* bias, float
 
 int modet_deconv4s2_bwd_data(const float* d_y, const float* y, const float* w, float* d_x, void* ws, size_t ws_bytes, int B, int D,
                              int H, int W, int Cin, int Cout, int act, float slope, modet_stream_t stream) {
-  MODET_CHECK_PTR(d_y); MODET_CHECK_PTR(w); MODET_CHECK_PTR(d_x); MODET_CHECK_PTR(ws);
-  int rc = covered(B, D, H, W, Cin, Cout);
-  if (rc == MODET_OK) rc = act_ok(act, slope);
+  const int rc = check_call(d_x, d_y, y, w, nullptr, ws, ws_bytes, modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, MODET_DECONV_PASS_BWD_DATA),
+                            covered(B, D, H, W, Cin, Cout), Cin, Cout, act, slope);
   if (rc != MODET_OK) return rc;
-  if (act == 1) MODET_CHECK_PTR(y);
-  if (!aligned_for(d_x, Cin) || !aligned_for(d_y, Cout) || (act == 1 && !aligned_for(y, Cout)) || !aligned4(w)) return MODET_ERR_UNSUPPORTED;
-  if (ws_bytes < modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, MODET_DECONV_PASS_BWD_DATA) || !aligned16(ws)) return MODET_ERR_WORKSPACE;
   const Dims s{B, D, H, W, Cin, Cout};
   hipStream_t st = (hipStream_t)stream;
   float* wd = (float*)ws;
-  hipLaunchKernelGGL(deconv_pack_kernel, dim3(blocks_for((int64_t)64 * pad4(Cin) * pad4(Cout))), dim3(BLK), 0, st, w, wd, Cin, Cout, 1);
+  launch_pack<FAMILY>(w, wd, Cin, Cout, 1, st);
   const int CiG = pad4(Cin) / 4;
   const bool vx = Cin % 4 == 0, vy = Cout % 4 == 0;
 #define LAUNCH_D4(TD_, TH_, TW_, ACT_, VX_, VY_)                                                                                \
@@ -473,14 +379,9 @@ int modet_deconv4s2_bwd_data(const float* d_y, const float* y, const float* w, f
 
 int modet_deconv4s2_bwd_weight(const float* x, const float* d_y, const float* y, float* d_w, float* d_b, void* ws, size_t ws_bytes,
                                int B, int D, int H, int W, int Cin, int Cout, int act, float slope, modet_stream_t stream) {
-  MODET_CHECK_PTR(x); MODET_CHECK_PTR(d_y); MODET_CHECK_PTR(d_w); MODET_CHECK_PTR(ws);
-  int rc = covered(B, D, H, W, Cin, Cout);
-  if (rc == MODET_OK) rc = act_ok(act, slope);
+  const int rc = check_call(x, d_y, y, d_w, d_b, ws, ws_bytes, modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, MODET_DECONV_PASS_BWD_WEIGHT),
+                            covered(B, D, H, W, Cin, Cout), Cin, Cout, act, slope);
   if (rc != MODET_OK) return rc;
-  if (act == 1) MODET_CHECK_PTR(y);
-  if (!aligned_for(x, Cin) || !aligned_for(d_y, Cout) || (act == 1 && !aligned_for(y, Cout)) || !aligned4(d_w) || !aligned4(d_b))
-    return MODET_ERR_UNSUPPORTED;
-  if (ws_bytes < modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, MODET_DECONV_PASS_BWD_WEIGHT) || !aligned16(ws)) return MODET_ERR_WORKSPACE;
   const Dims s{B, D, H, W, Cin, Cout};
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)ws;
@@ -500,11 +401,7 @@ int modet_deconv4s2_bwd_weight(const float* x, const float* d_y, const float* y,
   if (act) LAUNCH_W(true); else LAUNCH_W(false);
 #undef LAUNCH_W
 #undef LAUNCH_W3
-  const int64_t R = (int64_t)64 * pad4(Cin) * pad4(Cout) + pad4(Cout);
-  if (act)
-    hipLaunchKernelGGL(deconv_colsum_kernel<true>, dim3(blocks_for(R)), dim3(BLK), 0, st, (const float*)part, S, Cin, Cout, (double)slope, d_w, d_b);
-  else
-    hipLaunchKernelGGL(deconv_colsum_kernel<false>, dim3(blocks_for(R)), dim3(BLK), 0, st, (const float*)part, S, Cin, Cout, 0.0, d_w, d_b);
+  launch_colsum<FAMILY>(part, S, Cin, Cout, act, slope, d_w, d_b, st);
   return modet_launch_status();
 }
 

@@ -12,6 +12,7 @@ import ctypes
 import math
 import os
 import threading
+from typing import Callable, NamedTuple
 
 import torch
 from torch.autograd import Function
@@ -1285,6 +1286,7 @@ def posenc(x, Wt, b, alpha, tab):
 
 
 CONVS2_MAX_CHANNELS = 256        # MODET_CONVS2_MAX_CHANNELS of include/modet_hip_convs2.h
+DECONV_MAX_CHANNELS = 1024       # MODET_DECONV_MAX_CHANNELS of include/modet_hip_deconv.h
 
 
 def conv3d_s2_out_shape(D, H, W):
@@ -1292,84 +1294,146 @@ def conv3d_s2_out_shape(D, H, W):
     return tuple((int(n) - 1) // 2 + 1 for n in (D, H, W))
 
 
-def _convs2_args(op, x, w, b, slope):
-    """x (B,D,H,W,Cin); w (Cout,Cin,3,3,3); b (Cout,) or None; slope None or a float >= 0 -> (B, D, H, W, Cin, Cout, act, slope)"""
+def conv_transpose3d_k4s2_out_shape(D, H, W):
+    """the output grid of a 4x4x4 transposed convolution with stride 2 and padding 1: 2 n per axis"""
+    return tuple(2 * int(n) for n in (D, H, W))
+
+
+class _Strided(NamedTuple):
+    """One stride-2 layer family (csrc/strided.h has what their kernels share): all that differs between conv3d_s2 and
+    conv_transpose3d_k4s2 on the way to the library.  _strided_args and _StridedLayer do the rest once."""
+    op: str                  # the public wrapper, as the refusals name it
+    tag: str                 # the kernel-timer tags are <tag>_fwd[..], <tag>_bwd_data[..], <tag>_bwd_weight[..]
+    lib: str                 # the entry points are modet_<lib>_fwd, _bwd_data, _bwd_weight and _ws_bytes
+    kind: str                # what a bf16 feature handle is told the kernels are
+    w_shape: Callable        # (Cin, Cout) -> the weight's shape
+    cout_axis: int           # the axis of w that counts output channels
+    out_shape: Callable      # (D, H, W) -> the output grid
+    flops: Callable          # (Cin, Cout, input voxels, output voxels) -> of one pass
+    refusal: Callable        # (x, w, Cin, Cout) -> what is wrong with the channel counts or the grid, or None
+
+
+def _convs2_refusal(x, w, Cin, Cout):
+    if not (Cin == 1 or (Cin % 4 == 0 and Cin >= 4)) or Cin > CONVS2_MAX_CHANNELS:
+        return f"x has {Cin} channels: the kernels take 1 or a multiple of 4 up to {CONVS2_MAX_CHANNELS}"
+    if Cout % 4 != 0 or not 4 <= Cout <= CONVS2_MAX_CHANNELS:
+        return f"weight has {Cout} output channels: the kernels take a multiple of 4 up to {CONVS2_MAX_CHANNELS}"
+    if min(x.shape[:4]) < 1:
+        return f"x {tuple(x.shape)} is empty"
+    return None
+
+
+def _deconv_refusal(x, w, Cin, Cout):
+    if min(*x.shape, Cout) < 1:
+        return f"x {tuple(x.shape)} or weight {tuple(w.shape)} is empty"
+    if Cin > DECONV_MAX_CHANNELS:
+        return f"x has {Cin} channels: the kernels take 1 to {DECONV_MAX_CHANNELS}"
+    if Cout > DECONV_MAX_CHANNELS:
+        return f"weight has {Cout} output channels: the kernels take 1 to {DECONV_MAX_CHANNELS}"
+    return None
+
+
+_CONVS2 = _Strided("conv3d_s2", "convs2", "convs2", "stride-2 convolution", lambda Cin, Cout: (Cout, Cin, 3, 3, 3), 0, conv3d_s2_out_shape,
+                   lambda Cin, Cout, n_in, n_out: 54.0 * Cin * Cout * n_out, _convs2_refusal)
+_DECONV = _Strided("conv_transpose3d_k4s2", "deconv", "deconv4s2", "transposed-convolution", lambda Cin, Cout: (Cin, Cout, 4, 4, 4), 1,
+                   conv_transpose3d_k4s2_out_shape, lambda Cin, Cout, n_in, n_out: 128.0 * Cin * Cout * n_in, _deconv_refusal)
+
+
+def _strided_args(lay, op, x, w, b, slope):
+    """x (B,D,H,W,Cin); w lay.w_shape(Cin, Cout); b (Cout,) or None; slope None or a float >= 0 -> (B, D, H, W, Cin, Cout, act, slope)"""
     if getattr(x, "data16", None) is not None:
-        raise RuntimeError(f"{op}: x is a bf16 feature handle; the stride-2 convolution kernels are fp32 only")
+        raise RuntimeError(f"{op}: x is a bf16 feature handle; the {lay.kind} kernels are fp32 only")
     _chk(x, w, b)
     _rank5(op, "x", x)
     if w.dim() != 5:
-        raise RuntimeError(f"{op}: weight must be (Cout,Cin,3,3,3), got {tuple(w.shape)}")
+        raise RuntimeError(f"{op}: weight must be ({','.join(map(str, lay.w_shape('Cin', 'Cout')))}), got {tuple(w.shape)}")
     B, D, H, W, Cin = x.shape
-    Cout = w.shape[0]
-    _same_shape(op, "weight", w, (Cout, Cin, 3, 3, 3), f"x {tuple(x.shape)}")
+    Cout = w.shape[lay.cout_axis]
+    _same_shape(op, "weight", w, lay.w_shape(Cin, Cout), f"x {tuple(x.shape)}")
     _same_shape(op, "bias", b, (Cout,), f"weight {tuple(w.shape)}")
     if slope is not None and not (isinstance(slope, (int, float)) and not isinstance(slope, bool) and slope >= 0.0):
         raise RuntimeError(f"{op}: slope must be None (no activation) or a number >= 0 (0.0: ReLU), got {slope!r}")
-    if not (Cin == 1 or (Cin % 4 == 0 and Cin >= 4)) or Cin > CONVS2_MAX_CHANNELS:
-        raise RuntimeError(f"{op}: x has {Cin} channels: the kernels take 1 or a multiple of 4 up to {CONVS2_MAX_CHANNELS}")
-    if Cout % 4 != 0 or not 4 <= Cout <= CONVS2_MAX_CHANNELS:
-        raise RuntimeError(f"{op}: weight has {Cout} output channels: the kernels take a multiple of 4 up to {CONVS2_MAX_CHANNELS}")
-    if min(B, D, H, W) < 1:
-        raise RuntimeError(f"{op}: x {tuple(x.shape)} is empty")
-    if _L().modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, 0) == 0:
+    why = lay.refusal(x, w, Cin, Cout)
+    if why is not None:
+        raise RuntimeError(f"{op}: {why}")
+    if getattr(_L(), f"modet_{lay.lib}_ws_bytes")(B, D, H, W, Cin, Cout, 0) == 0:
         raise RuntimeError(f"{op}: x {tuple(x.shape)} -> {Cout} channels: a tensor of 2^31 elements or more (the kernels' limit)")
     return B, D, H, W, Cin, Cout, int(slope is not None), float(slope or 0.0)
 
 
-class _Conv3dS2(Function):
-    """nn.Conv3d(Cin, Cout, 3, stride=2, padding=1) [+ LeakyReLU(slope)] on channels-last voxels; the backward folds the
-    activation's derivative into its d_y loads and skips the data gradient of an input that needs none (the image)."""
+def _convs2_args(op, x, w, b, slope):
+    """x (B,D,H,W,Cin); w (Cout,Cin,3,3,3); b (Cout,) or None; slope None or a float >= 0 -> (B, D, H, W, Cin, Cout, act, slope)"""
+    return _strided_args(_CONVS2, op, x, w, b, slope)
+
+
+def _deconv_args(op, x, w, b, slope):
+    """x (B,D,H,W,Cin); w (Cin,Cout,4,4,4); b (Cout,) or None; slope None or a float >= 0 -> (B, D, H, W, Cin, Cout, act, slope)"""
+    return _strided_args(_DECONV, op, x, w, b, slope)
+
+
+class _StridedLayer(Function):
+    """nn.Conv3d(Cin, Cout, 3, stride=2, padding=1) or nn.ConvTranspose3d(Cin, Cout, 4, stride=2, padding=1) [+ LeakyReLU(slope)]
+    on channels-last voxels, by ``lay``; the backward folds the activation's derivative into its d_y loads and skips the data
+    gradient of an input that needs none (the image)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, slope):
-        B, D, H, W, Cin, Cout, act, sl = _convs2_args("conv3d_s2", x, w, b, slope)
+    def forward(ctx, lay, x, w, b, slope):
+        B, D, H, W, Cin, Cout, act, sl = _strided_args(lay, lay.op, x, w, b, slope)
         L = _L()
-        Do, Ho, Wo = conv3d_s2_out_shape(D, H, W)
-        y = torch.empty((B, Do, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-        nb = L.modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, 0)
+        y = torch.empty((B, *lay.out_shape(D, H, W), Cout), dtype=torch.float32, device=x.device)
+        nb = getattr(L, f"modet_{lay.lib}_ws_bytes")(B, D, H, W, Cin, Cout, 0)
         ws = _ws(nb, x)
-        with _Guard(x, f"convs2_fwd[{Cin}->{Cout}]", 54.0 * Cin * Cout * B * Do * Ho * Wo, 4.0 * (x.numel() + y.numel())):
-            _call(L.modet_convs2_fwd, _p(x), _p(w), _p(b), _p(y), _p(ws), nb, B, D, H, W, Cin, Cout, act, sl, _stream())
+        with _Guard(x, f"{lay.tag}_fwd[{Cin}->{Cout}]", lay.flops(Cin, Cout, B * D * H * W, y.numel() // Cout), 4.0 * (x.numel() + y.numel())):
+            _call(getattr(L, f"modet_{lay.lib}_fwd"), _p(x), _p(w), _p(b), _p(y), _p(ws), nb, B, D, H, W, Cin, Cout, act, sl, _stream())
         ctx.save_for_backward(x, w, b, y if act else None)
-        ctx.act, ctx.slope, ctx.step = act, sl, current_step()
+        ctx.lay, ctx.act, ctx.slope, ctx.step = lay, act, sl, current_step()
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, b, y = ctx.saved_tensors
         B, D, H, W, Cin = x.shape
-        Cout, L = w.shape[0], _L()
+        lay, L = ctx.lay, _L()
+        Cout = w.shape[lay.cout_axis]
         dy = dy.contiguous()
         dims = (B, D, H, W, Cin, Cout, ctx.act, ctx.slope)
-        n_out = float(dy.numel() // Cout)
+        flops = lay.flops(Cin, Cout, float(x.numel() // Cin), float(dy.numel() // Cout))
+        nbytes = 4.0 * (x.numel() + (1 + ctx.act) * dy.numel())
+        need_x, need_w, need_b = ctx.needs_input_grad[1:4]
         dx = None
-        if ctx.needs_input_grad[0]:
+        if need_x:
             dx = torch.empty_like(x)
-            nb = L.modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, 1)
+            nb = getattr(L, f"modet_{lay.lib}_ws_bytes")(B, D, H, W, Cin, Cout, 1)
             ws = _ws(nb, x)
-            with _Guard(x, f"convs2_bwd_data[{Cout}->{Cin}]", 54.0 * Cin * Cout * n_out, 4.0 * (x.numel() + (1 + ctx.act) * dy.numel())):
-                _call(L.modet_convs2_bwd_data, _p(dy), _p(y), _p(w), _p(dx), _p(ws), nb, *dims, _stream())
+            with _Guard(x, f"{lay.tag}_bwd_data[{Cout}->{Cin}]", flops, nbytes):
+                _call(getattr(L, f"modet_{lay.lib}_bwd_data"), _p(dy), _p(y), _p(w), _p(dx), _p(ws), nb, *dims, _stream())
         ret = [None, None]
-        if ctx.needs_input_grad[1] or (b is not None and ctx.needs_input_grad[2]):
+        if need_w or (b is not None and need_b):
             # written straight into the step's gradient buffer where the scope hands out destinations; the launch reduces its own
             # partial rows (DESIGN.md 4.11)
             params = (w,) if b is None else (w, b)
             dsts, _, back = _param_dsts(ctx.step, *params)
             ret = list(back) + [None] * (2 - len(back))
-            nb = L.modet_convs2_ws_bytes(B, D, H, W, Cin, Cout, 2)
+            nb = getattr(L, f"modet_{lay.lib}_ws_bytes")(B, D, H, W, Cin, Cout, 2)
             ws = _ws(nb, x)
-            with _Guard(x, f"convs2_bwd_weight[{Cin}->{Cout}]", 54.0 * Cin * Cout * n_out, 4.0 * (x.numel() + (1 + ctx.act) * dy.numel())):
-                _call(L.modet_convs2_bwd_weight, _p(x), _p(dy), _p(y), _p(dsts[0]), _p(dsts[1] if b is not None else None), _p(ws), nb,
-                      *dims, _stream())
-        return (dx, ret[0], ret[1], None)
+            with _Guard(x, f"{lay.tag}_bwd_weight[{Cin}->{Cout}]", flops, nbytes):
+                _call(getattr(L, f"modet_{lay.lib}_bwd_weight"), _p(x), _p(dy), _p(y), _p(dsts[0]), _p(dsts[1] if b is not None else None),
+                      _p(ws), nb, *dims, _stream())
+        return (None, dx, ret[0], ret[1], None)
 
 
 def conv3d_s2(x, w, b=None, slope=None):
     """3x3x3 convolution with stride 2 and padding 1 on channels-last voxels, then LeakyReLU(slope) (slope=None: no activation,
     0.0: ReLU) -- the ConvBlock(cin, cout, 3, 2, 1) of the RDN / PCNet / PR++ encoders ("Baseline methods/RDN/models.py":172-192).
     x (B,D,H,W,Cin) -> (B,Do,Ho,Wo,Cout), conv3d_s2_out_shape."""
-    return _Conv3dS2.apply(x, w, b, slope)
+    return _StridedLayer.apply(_CONVS2, x, w, b, slope)
+
+
+def conv_transpose3d_k4s2(x, w, b=None, slope=None):
+    """4x4x4 transposed convolution with stride 2 and padding 1 on channels-last voxels, then LeakyReLU(slope) (slope=None: no
+    activation, 0.0: ReLU) -- the upsampling layer of the RCN / VTN decoder ("Baseline methods/RCN/models.py": ConvTranspose3d(4,
+    stride=2) and the crop [1:-1] of every axis, the same function).  x (B,D,H,W,Cin), w (Cin,Cout,4,4,4) -> (B,2D,2H,2W,Cout)."""
+    return _StridedLayer.apply(_DECONV, x, w, b, slope)
 
 
 class _CatChannels(Function):
@@ -1409,93 +1473,6 @@ def cat_channels(a, b):
     """torch.cat([a, b], -1) of two channels-last tensors (RDN's Estimator input, "Baseline methods/RDN/models.py":211-214: the
     reference concatenates along dim 1 of its planar layout); the backward splits the gradient"""
     return _CatChannels.apply(a, b)
-
-
-DECONV_MAX_CHANNELS = 1024       # MODET_DECONV_MAX_CHANNELS of include/modet_hip_deconv.h
-
-
-def conv_transpose3d_k4s2_out_shape(D, H, W):
-    """the output grid of a 4x4x4 transposed convolution with stride 2 and padding 1: 2 n per axis"""
-    return tuple(2 * int(n) for n in (D, H, W))
-
-
-def _deconv_args(op, x, w, b, slope):
-    """x (B,D,H,W,Cin); w (Cin,Cout,4,4,4); b (Cout,) or None; slope None or a float >= 0 -> (B, D, H, W, Cin, Cout, act, slope)"""
-    if getattr(x, "data16", None) is not None:
-        raise RuntimeError(f"{op}: x is a bf16 feature handle; the transposed-convolution kernels are fp32 only")
-    _chk(x, w, b)
-    _rank5(op, "x", x)
-    if w.dim() != 5:
-        raise RuntimeError(f"{op}: weight must be (Cin,Cout,4,4,4), got {tuple(w.shape)}")
-    B, D, H, W, Cin = x.shape
-    Cout = w.shape[1]
-    _same_shape(op, "weight", w, (Cin, Cout, 4, 4, 4), f"x {tuple(x.shape)}")
-    _same_shape(op, "bias", b, (Cout,), f"weight {tuple(w.shape)}")
-    if slope is not None and not (isinstance(slope, (int, float)) and not isinstance(slope, bool) and slope >= 0.0):
-        raise RuntimeError(f"{op}: slope must be None (no activation) or a number >= 0 (0.0: ReLU), got {slope!r}")
-    if min(B, D, H, W, Cin, Cout) < 1:
-        raise RuntimeError(f"{op}: x {tuple(x.shape)} or weight {tuple(w.shape)} is empty")
-    if Cin > DECONV_MAX_CHANNELS:
-        raise RuntimeError(f"{op}: x has {Cin} channels: the kernels take 1 to {DECONV_MAX_CHANNELS}")
-    if Cout > DECONV_MAX_CHANNELS:
-        raise RuntimeError(f"{op}: weight has {Cout} output channels: the kernels take 1 to {DECONV_MAX_CHANNELS}")
-    if _L().modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, 0) == 0:
-        raise RuntimeError(f"{op}: x {tuple(x.shape)} -> {Cout} channels: a tensor of 2^31 elements or more (the kernels' limit)")
-    return B, D, H, W, Cin, Cout, int(slope is not None), float(slope or 0.0)
-
-
-class _ConvTranspose3dK4S2(Function):
-    """nn.ConvTranspose3d(Cin, Cout, 4, stride=2, padding=1) [+ LeakyReLU(slope)] on channels-last voxels; the backward folds the
-    activation's derivative into its d_y loads and skips the data gradient of an input that needs none."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, slope):
-        B, D, H, W, Cin, Cout, act, sl = _deconv_args("conv_transpose3d_k4s2", x, w, b, slope)
-        L = _L()
-        y = torch.empty((B, 2 * D, 2 * H, 2 * W, Cout), dtype=torch.float32, device=x.device)
-        nb = L.modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, 0)
-        ws = _ws(nb, x)
-        with _Guard(x, f"deconv_fwd[{Cin}->{Cout}]", 128.0 * Cin * Cout * B * D * H * W,4.0 * (x.numel() + y.numel())):
-            _call(L.modet_deconv4s2_fwd, _p(x), _p(w), _p(b), _p(y), _p(ws), nb, B, D, H, W, Cin, Cout, act, sl, _stream())
-        ctx.save_for_backward(x, w, b, y if act else None)
-        ctx.act, ctx.slope, ctx.step = act, sl, current_step()
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w, b, y = ctx.saved_tensors
-        B, D, H, W, Cin = x.shape
-        Cout, L = w.shape[1], _L()
-        dy = dy.contiguous()
-        dims = (B, D, H, W, Cin, Cout, ctx.act, ctx.slope)
-        flops = 128.0 * Cin * Cout * (x.numel() // Cin)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            nb = L.modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, 1)
-            ws = _ws(nb, x)
-            with _Guard(x, f"deconv_bwd_data[{Cout}->{Cin}]", flops, 4.0 * (x.numel() + (1 + ctx.act) * dy.numel())):
-                _call(L.modet_deconv4s2_bwd_data, _p(dy), _p(y), _p(w), _p(dx), _p(ws), nb, *dims, _stream())
-        ret = [None, None]
-        if ctx.needs_input_grad[1] or (b is not None and ctx.needs_input_grad[2]):
-            # written straight into the step's gradient buffer where the scope hands out destinations; the launch reduces its own
-            # partial rows, as the stride-2 convolution's (DESIGN.md 4.11, 4.12)
-            params = (w,) if b is None else (w, b)
-            dsts, _, back = _param_dsts(ctx.step, *params)
-            ret = list(back) + [None] * (2 - len(back))
-            nb = L.modet_deconv4s2_ws_bytes(B, D, H, W, Cin, Cout, 2)
-            ws = _ws(nb, x)
-            with _Guard(x, f"deconv_bwd_weight[{Cin}->{Cout}]", flops, 4.0 * (x.numel() + (1 + ctx.act) * dy.numel())):
-                _call(L.modet_deconv4s2_bwd_weight, _p(x), _p(dy), _p(y), _p(dsts[0]), _p(dsts[1] if b is not None else None), _p(ws),
-                      nb, *dims, _stream())
-        return (dx, ret[0], ret[1], None)
-
-
-def conv_transpose3d_k4s2(x, w, b=None, slope=None):
-    """4x4x4 transposed convolution with stride 2 and padding 1 on channels-last voxels, then LeakyReLU(slope) (slope=None: no
-    activation, 0.0: ReLU) -- the upsampling layer of the RCN / VTN decoder ("Baseline methods/RCN/models.py": ConvTranspose3d(4,
-    stride=2) and the crop [1:-1] of every axis, the same function).  x (B,D,H,W,Cin), w (Cin,Cout,4,4,4) -> (B,2D,2H,2W,Cout)."""
-    return _ConvTranspose3dK4S2.apply(x, w, b, slope)
 
 
 def _na_args(op, C, heads, rpb, bf16):

@@ -10,54 +10,13 @@ import torch
 
 from tests import guard
 from tests import rdn_oracle as orc
-from tests.guard_family import Harness, stream
+from tests.guard_family import DIM, NULL, UNSUP, Harness, StridedLayer, stream
 
 pytestmark = pytest.mark.gpu
 
 H = Harness("convs2")
 px = H.fixture()
-
-
-def abi_case(n, bias=True):
-    """the C ABI directly, exact workspaces: forward, data gradient, weight gradient"""
-    def case(g):
-        from smilecode_amd import _lib
-        L = _lib.load()
-        B, (D_, H_, W_), Cin, Cout, slope = orc.OP_CASES[n]
-        x, w, b, gy = (g(t) for t in orc.case_tensors(n))
-        b = b if bias else None
-        act, sl = int(slope is not None), float(slope or 0.0)
-        dims = (B, D_, H_, W_, Cin, Cout)
-        y, dx, dw = g.empty(gy.shape), g.empty(x.shape), g.empty(w.shape)
-        db = g.empty((Cout,)) if bias else None
-        p = lambda v: None if v is None else v.data_ptr()      # noqa: E731
-        nbs = [L.modet_convs2_ws_bytes(*dims, k) for k in range(3)]
-        assert min(nbs) > 0
-        ws = [g.ws(nb) for nb in nbs]
-        _lib.check(L.modet_convs2_fwd(p(x), p(w), p(b), p(y), p(ws[0]), nbs[0], *dims, act, sl, stream()), "convs2 fwd")
-        ya = y if act else None
-        _lib.check(L.modet_convs2_bwd_data(p(gy), p(ya), p(w), p(dx), p(ws[1]), nbs[1], *dims, act, sl, stream()), "convs2 bwd data")
-        _lib.check(L.modet_convs2_bwd_weight(p(x), p(gy), p(ya), p(dw), p(db), p(ws[2]), nbs[2], *dims, act, sl, stream()), "convs2 bwd weight")
-        out = {"y": y, "d_x": dx, "d_w": dw}
-        if bias:
-            out["d_b"] = db
-        return out
-    return case
-
-
-def ops_case(n, bias=True):
-    """the package's own wrapper under GuardedAlloc: outputs, gradients and workspaces are guarded allocations"""
-    def case(g):
-        from smilecode_amd import ops
-        slope = orc.OP_CASES[n][4]
-        x, w, b, gy = (g(t) for t in orc.case_tensors(n, seed=2000 + n))
-        leaves = [t.requires_grad_(True) for t in ((x, w, b) if bias else (x, w))]
-        y = ops.conv3d_s2(x, w, b if bias else None, slope)
-        grads = torch.autograd.grad(y, leaves, gy)
-        out = {"y": y}
-        out.update({"g%d" % i: v for i, v in enumerate(grads)})
-        return out
-    return case
+S = StridedLayer(orc, "convs2", "conv3d_s2", has_bias=lambda n: True, seed=2000)
 
 
 def cat_abi_case(shape, C1, C2, want=(True, True)):
@@ -94,10 +53,10 @@ def cat_ops_case(shape, C1, C2):
 
 CASES = {}
 for _n in (1, 3, 4, 6):
-    CASES["abi[case%d]" % _n] = abi_case(_n)
-    CASES["ops[case%d]" % _n] = ops_case(_n)
-CASES["abi[case6,no bias]"] = abi_case(6, bias=False)
-CASES["ops[case1,no bias]"] = ops_case(1, bias=False)
+    CASES["abi[case%d]" % _n] = S.abi_case(_n)
+    CASES["ops[case%d]" % _n] = S.ops_case(_n)
+CASES["abi[case6,no bias]"] = S.abi_case(6, bias=False)
+CASES["ops[case1,no bias]"] = S.ops_case(1, bias=False)
 CASES["cat abi[3x5x7,8+16]"] = cat_abi_case((1, 3, 5, 7), 8, 16)
 CASES["cat abi[3x3x3,3+5]"] = cat_abi_case((2, 3, 3, 3), 3, 5)
 CASES["cat abi[3x5x7,4+12,d_a only]"] = cat_abi_case((1, 3, 5, 7), 4, 12, want=(True, False))
@@ -134,48 +93,21 @@ def test_wrappers_refuse_before_any_launch(px):
 def test_library_refuses_with_error_codes():
     """NULL pointers, channel counts outside the kernels', empty axes, a negative slope, a misaligned tensor and a short or misaligned
     workspace are answered with the library's error codes before any launch: the outputs keep their fill"""
-    from smilecode_amd import _lib
-    L = _lib.load()
-    dims = (1, 4, 4, 4, 4, 8)
-    x, w, b = torch.zeros(1, 4, 4, 4, 4, device="cuda"), torch.zeros(8, 4, 3, 3, 3, device="cuda"), torch.zeros(8, device="cuda")
-    y, gy = torch.full((1, 2, 2, 2, 8), 7.0, device="cuda"), torch.ones(1, 2, 2, 2, 8, device="cuda")
-    dx, dw, db = torch.full_like(x, 7.0), torch.full_like(w, 7.0), torch.full_like(b, 7.0)
-    P, st = (lambda t: t.data_ptr()), stream()
-    NULL, DIM, UNSUP, WS = -1, -2, -3, -4
-    nb = [L.modet_convs2_ws_bytes(*dims, k) for k in range(3)]
-    assert nb[0] == nb[1] == 27 * 4 * 8 * 4 and nb[2] == 2 * (27 * 4 * 8 + 8) * 4
-    assert L.modet_convs2_ws_bytes(*dims, 3) == 0 and L.modet_convs2_ws_bytes(1, 4, 4, 4, 2, 8, 0) == 0
-    assert L.modet_convs2_ws_bytes(1, 4, 4, 4, 4, 260, 0) == 0 and L.modet_convs2_ws_bytes(1, 0, 4, 4, 4, 8, 0) == 0
-    assert L.modet_convs2_ws_bytes(1, 1024, 1024, 1024, 4, 8, 0) == 0                      # x of 2^32 elements
-    ws = torch.empty(max(nb) + 32, dtype=torch.uint8, device="cuda")
-    tail = (1, 0.2, st)
-    assert L.modet_convs2_fwd(None, P(w), P(b), P(y), P(ws), nb[0], *dims, *tail) == NULL
-    assert L.modet_convs2_fwd(P(x), P(w), P(b), None, P(ws), nb[0], *dims, *tail) == NULL
-    assert L.modet_convs2_fwd(P(x), P(w), P(b), P(y), None, nb[0], *dims, *tail) == NULL
-    assert L.modet_convs2_fwd(P(x), P(w), P(b), P(y), P(ws), nb[0] - 1, *dims, *tail) == WS
-    assert L.modet_convs2_fwd(P(x), P(w), P(b), P(y), P(ws) + 4, nb[0], *dims, *tail) == WS
-    assert L.modet_convs2_fwd(P(x) + 4, P(w), P(b), P(y), P(ws), nb[0], *dims, *tail) == UNSUP
-    assert L.modet_convs2_fwd(P(x), P(w), P(b), P(y), P(ws), nb[0], 1, 4, 4, 4, 3, 8, *tail) == UNSUP
-    assert L.modet_convs2_fwd(P(x), P(w), P(b), P(y), P(ws), nb[0], 1, 4, 4, 4, 4, 6, *tail) == UNSUP
-    assert L.modet_convs2_fwd(P(x), P(w), P(b), P(y), P(ws), nb[0], 1, 4, 0, 4, 4, 8, *tail) == DIM
-    assert L.modet_convs2_fwd(P(x), P(w), P(b), P(y), P(ws), nb[0], *dims, 1, -0.5, st) == UNSUP
-    assert L.modet_convs2_fwd(P(x), P(w), P(b), P(y), P(ws), nb[0], *dims, 2, 0.2, st) == UNSUP
-    assert L.modet_convs2_bwd_data(P(gy), None, P(w), P(dx), P(ws), nb[1], *dims, *tail) == NULL      # act == 1 needs y
-    assert L.modet_convs2_bwd_data(P(gy), P(y), P(w), None, P(ws), nb[1], *dims, *tail) == NULL
-    assert L.modet_convs2_bwd_data(P(gy), P(y), P(w), P(dx), P(ws), nb[1] - 4, *dims, *tail) == WS
-    assert L.modet_convs2_bwd_weight(P(x), P(gy), None, P(dw), P(db), P(ws), nb[2], *dims, *tail) == NULL
-    assert L.modet_convs2_bwd_weight(P(x), P(gy), P(y), None, P(db), P(ws), nb[2], *dims, *tail) == NULL
-    assert L.modet_convs2_bwd_weight(P(x), P(gy), P(y), P(dw), P(db), P(ws), nb[2] - 4, *dims, *tail) == WS
-    assert L.modet_convs2_bwd_weight(P(x), P(gy), P(y), P(dw), P(db), P(ws) + 8, nb[2], *dims, *tail) == WS
+    c = S.refusals((1, 4, 4, 4, 4, 8), (8, 4, 3, 3, 3), slope=0.2)
+    L, P, st, ws_bytes = c.L, (lambda t: t.data_ptr()), stream(), c.L.modet_convs2_ws_bytes
+    assert c.nb[0] == c.nb[1] == 27 * 4 * 8 * 4 and c.nb[2] == 2 * (27 * 4 * 8 + 8) * 4
+    assert ws_bytes(*c.dims, 3) == 0 and ws_bytes(1, 4, 4, 4, 2, 8, 0) == 0
+    assert ws_bytes(1, 4, 4, 4, 4, 260, 0) == 0 and ws_bytes(1, 0, 4, 4, 4, 8, 0) == 0
+    assert ws_bytes(1, 1024, 1024, 1024, 4, 8, 0) == 0                                     # x of 2^32 elements
+    assert c.fwd(dims=(1, 4, 4, 4, 3, 8)) == UNSUP and c.fwd(dims=(1, 4, 4, 4, 4, 6)) == UNSUP
+    x, dx = c.x, c.dx
     assert L.modet_cat_channels2_fwd(P(x), None, P(dx), 64, 4, 4, st) == NULL
     assert L.modet_cat_channels2_fwd(P(x), P(x), P(dx), 0, 4, 4, st) == DIM
     assert L.modet_cat_channels2_fwd(P(x), P(x), P(dx), 8, 4, 0, st) == DIM
     assert L.modet_cat_channels2_fwd(P(x), P(x), P(dx), 1 << 29, 4, 4, st) == DIM
     assert L.modet_cat_channels2_bwd(P(x), None, None, 8, 4, 4, st) == NULL
     assert L.modet_cat_channels2_bwd(P(x) + 4, P(dx), None, 8, 4, 4, st) == UNSUP
-    torch.cuda.synchronize()
-    for t in (y, dx, dw, db):
-        assert bool((t == 7.0).all())                                   # nothing was launched
+    c.check()
 
 
 def test_every_launching_convs2_entry_point_ran_between_guard_bands(px):
