@@ -22,9 +22,25 @@ OP_CASES = {
     5: (2, (5, 6, 7), 19, 3, False, None),      # Pred0
     6: (1, (9, 17, 33), 8, 4, True, 0.1),       # several tiles, a partial one in every axis
     7: (1, (4, 4, 4), 1, 1, True, None),        # the smallest channel counts
+    # (N = B D H W input voxels; the weight gradient makes S = ceil(N / max(256, ceil(N / 256))) partial rows)
+    8: (1, (9, 11, 12), 8, 8, True, 0.1),       # 4x4x8 forward tile, 3x3x2 tiles, partial in D and H; N = 1188: S = 5
+    9: (2, (7, 8, 14), 20, 6, True, 0.1),       # activation with a Cout tail, chunks of 16 + 4, 4x4x4 data-gradient tiles; S = 7
+    10: (1, (6, 7, 9), 35, 8, True, 0.1),       # the network's Deconv2: chunks of 16 + 16 + 3, 9 input-channel groups
+    11: (1, (5, 6, 9), 24, 20, True, 0.1),      # 4x4x4 forward tile, 2x2x3 tiles with partial ones, a last chunk of 8
+    12: (1, (5, 6, 9), 24, 13, True, 0.1),      # 4x4x4 forward tile with a Cout tail and an activation
+    13: (1, (41, 40, 41), 2, 3, False, None),   # N = 67 240 > 65 536: splits of 263 voxels, S = 256, the last one of 175
 }
 MASK_BELOW = 1e-5          # |y| in fp64 below which the two precisions may take different LeakyReLU branches
 MASK_CAP = 0.01            # at most this share of a case's outputs may lose its cotangent
+
+# the variant sweep of tests/test_gpu_deconv.py: one sample of SWEEP_GRID with a bias at every (Cin, Cout, slope) of the product
+SWEEP_GRID = (5, 9, 9)
+SWEEP_CIN, SWEEP_COUT, SWEEP_SLOPES = (3, 8, 12, 27), (3, 4, 6, 8, 12, 13), (None, 0.1)
+
+
+def sweep_spec(Cin, Cout, slope):
+    """(spec, seed) of a sweep combination for spec_tensors"""
+    return (1, SWEEP_GRID, Cin, Cout, True, slope), 5000 + 40 * Cin + Cout + (0 if slope is None else 20)
 
 
 def out_shape(D, H, W):
@@ -84,9 +100,11 @@ def op_value_and_grads(x, w, b, gy, slope, dtype):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(n, kind, seed):
-    B, (D, H, W), Cin, Cout, bias, slope = OP_CASES[n]
-    g = torch.Generator().manual_seed(3000 + n if seed is None else seed)
+def spec_tensors(spec, seed, kind="randn"):
+    """(x, w, b, gy, masked share) of a layer (B, (D, H, W), Cin, Cout, bias, slope) that need not be in OP_CASES, as case_tensors
+    and masked_share describe them"""
+    B, (D, H, W), Cin, Cout, bias, slope = spec
+    g = torch.Generator().manual_seed(seed)
     shapes = ((B, D, H, W, Cin), (Cin, Cout, 4, 4, 4), (Cout,), (B, 2 * D, 2 * H, 2 * W, Cout))
     if kind == "int":
         x, w, b, gy = (torch.randint(-3, 4, s, generator=g).float() for s in shapes)
@@ -106,12 +124,12 @@ def case_tensors(n, kind="randn", seed=None):
     """(x, w, b, gy) of case n in fp32; b is None for a case without a bias.  kind 'randn': unit-variance data, weights scaled by
     1/sqrt(8 Cin) (8 taps reach an output voxel), the cotangent zeroed where |y| < MASK_BELOW in fp64; 'int': integers in [-3, 3],
     every product and partial sum exactly representable in fp32"""
-    return _case(n, kind, seed)[:4]
+    return spec_tensors(OP_CASES[n], 3000 + n if seed is None else seed, kind)[:4]
 
 
 def masked_share(n, seed=None):
     """the share of case n's outputs whose cotangent case_tensors zeroed (at most MASK_CAP: tests/test_cpu_rcn.py)"""
-    return _case(n, "randn", seed)[4]
+    return spec_tensors(OP_CASES[n], 3000 + n if seed is None else seed, "randn")[4]
 
 
 # ------------------------------------------------------------------------------------------------ the network

@@ -5,6 +5,7 @@ dict, differentiable through autograd, in fp64 (the reference for every bound) o
 composition loses in single precision).  nn.Conv3d in fp64 IS the reference's layer, so the op needs no committed fixture.
 
 The cases of tests/test_gpu_convs2.py and tests/test_gpu_convs2_guard.py live here, so that both build the same tensors."""
+import functools
 import math
 
 import torch
@@ -22,7 +23,15 @@ OP_CASES = {
     5: (2, (5, 4, 9), 8, 4, 0.0),           # ReLU, Cout < Cin
     6: (1, (9, 17, 33), 4, 8, 0.1),         # several workgroups and a partial last one in each of the three kernels
     7: (1, (4, 4, 6), 256, 256, 0.2),       # the channel limit
+    # (N = B Do Ho Wo output voxels; the weight gradient makes S = ceil(N / V) partial rows, V = 256, 512 or 1024 by Cout)
+    8: (2, (9, 17, 33), 1, 8, None),        # Cin = 1 without an activation; N = 1530: S = 6
+    9: (1, (16, 18, 20), 8, 128, 0.2),      # V = 512 with N = 720: two splits, the last one partial
+    10: (2, (17, 20, 24), 4, 256, 0.2),     # V = 1024 with N = 2160: three splits, the last one partial, across the batch boundary
+    11: (1, (20, 22, 30), 4, 4, 0.1),       # N = 1650: S = 7
 }
+MASKED_FROM = 8            # cases from this number on zero the cotangent near y = 0 (cases 1 .. 7 keep the tensors they always had)
+MASK_BELOW = 1e-5          # |y| in fp64 below which the two precisions may take different LeakyReLU branches (tests/rcn_oracle.py's)
+MASK_CAP = 0.01            # at most this share of a case's outputs may lose its cotangent
 
 
 def out_shape(D, H, W):
@@ -51,17 +60,37 @@ def op_value_and_grads(x, w, b, gy, slope, dtype):
     return {"y": y.detach(), "d_x": dx, "d_w": dw, "d_b": db}
 
 
-def case_tensors(n, kind="randn", seed=None):
-    """(x, w, b, gy) of case n in fp32.  kind 'randn': unit-variance data, weights scaled by 1/sqrt(27 Cin); 'int': integers in
-    [-3, 3], every product and partial sum exactly representable in fp32"""
-    B, (D, H, W), Cin, Cout, _ = OP_CASES[n]
-    g = torch.Generator().manual_seed(1000 + n if seed is None else seed)
+@functools.lru_cache(maxsize=None)
+def spec_tensors(spec, seed, kind="randn", mask=False):
+    """(x, w, b, gy, masked share) of a layer (B, (D, H, W), Cin, Cout, slope) that need not be in OP_CASES, as case_tensors
+    describes them; mask: zero the cotangent where |y| < MASK_BELOW in fp64 (an fp32 / fp64 LeakyReLU branch flip there is no
+    kernel error)"""
+    B, (D, H, W), Cin, Cout, slope = spec
+    g = torch.Generator().manual_seed(seed)
     Do, Ho, Wo = out_shape(D, H, W)
     shapes = ((B, D, H, W, Cin), (Cout, Cin, 3, 3, 3), (Cout,), (B, Do, Ho, Wo, Cout))
     if kind == "int":
-        return tuple(torch.randint(-3, 4, s, generator=g).float() for s in shapes)
+        return tuple(torch.randint(-3, 4, s, generator=g).float() for s in shapes) + (0.0,)
     x, w, b, gy = (torch.randn(s, generator=g) for s in shapes)
-    return x, w * (1.0 / math.sqrt(27 * Cin)), b * 0.1, gy
+    w, b = w * (1.0 / math.sqrt(27 * Cin)), b * 0.1
+    masked = 0.0
+    if mask and slope is not None:
+        near = conv_s2_cl(x.double(), w.double(), b.double(), slope).abs() < MASK_BELOW
+        masked = float(near.double().mean())
+        gy = torch.where(near, torch.zeros_like(gy), gy).contiguous()      # (near has the permuted strides of y: where() follows them)
+    return x, w, b, gy, masked
+
+
+def case_tensors(n, kind="randn", seed=None):
+    """(x, w, b, gy) of case n in fp32.  kind 'randn': unit-variance data, weights scaled by 1/sqrt(27 Cin), from case MASKED_FROM
+    on the cotangent zeroed where |y| < MASK_BELOW in fp64; 'int': integers in [-3, 3], every product and partial sum exactly
+    representable in fp32"""
+    return spec_tensors(OP_CASES[n], 1000 + n if seed is None else seed, kind, n >= MASKED_FROM)[:4]
+
+
+def masked_share(n, seed=None):
+    """the share of case n's outputs whose cotangent case_tensors zeroed (at most MASK_CAP: tests/test_cpu_rdn.py)"""
+    return spec_tensors(OP_CASES[n], 1000 + n if seed is None else seed, "randn", n >= MASKED_FROM)[4]
 
 
 # ------------------------------------------------------------------------------------------------ the network

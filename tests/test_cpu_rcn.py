@@ -11,7 +11,7 @@ import torch
 
 from tests import guard, rcn_oracle as orc
 from tests.guard_family import check_family_table, check_header_is_c99
-from tests.util import GOLD, gold
+from tests.util import GOLD, digest, gold
 
 NAMES = {"modet_deconv4s2_ws_bytes", "modet_deconv4s2_fwd", "modet_deconv4s2_bwd_data", "modet_deconv4s2_bwd_weight"}
 NPZ = "e2e_rcn_64x64x128.npz"
@@ -112,6 +112,34 @@ def test_masked_share_of_every_case_is_below_the_cap():
         share = orc.masked_share(n)
         assert 0.0 <= share <= orc.MASK_CAP, (n, share)
         assert share == 0.0 or case[5] is not None
+    for cin in orc.SWEEP_CIN:                               # the variant sweep of tests/test_gpu_deconv.py, at its own seeds
+        for cout in orc.SWEEP_COUT:
+            for slope in orc.SWEEP_SLOPES:
+                share = orc.spec_tensors(*orc.sweep_spec(cin, cout, slope))[4]
+                assert 0.0 <= share <= orc.MASK_CAP and (share == 0.0 or slope is not None), (cin, cout, slope, share)
+    seeds = [orc.sweep_spec(ci, co, s)[1] for ci in orc.SWEEP_CIN for co in orc.SWEEP_COUT for s in orc.SWEEP_SLOPES]
+    assert len(set(seeds)) == 48 and not set(seeds) & {3000 + n for n in orc.OP_CASES}
+
+
+def test_tensors_of_cases_1_to_7_are_what_they_always_were():
+    """goldens, guard files and the frozen yardstick of tests/test_gpu_deconv.py rest on these tensors: a checksum taken before
+    the case table grew and tensor construction moved into spec_tensors"""
+    assert digest(t for n in range(1, 8) for kind in ("randn", "int") for t in orc.case_tensors(n, kind)) == \
+        "b5d675798a369486a1b7c3d1882303ec5e7a5209a3c2dd4cef566891c5e70abd"
+
+
+def test_new_cases_launch_what_they_are_named_for():
+    """the arithmetic behind the comments of OP_CASES 8 .. 13: the weight gradient's row counts and the last split"""
+    rows = {}
+    for n, (B, (D, H, W), _, _, _, _) in orc.OP_CASES.items():
+        N = B * D * H * W
+        V = max(256, -(-N // 256))
+        rows[n] = (-(-N // V), N - (-(-N // V) - 1) * V)
+    assert {n: rows[n][0] for n in (8, 9, 13)} == {8: 5, 9: 7, 13: 256} and rows[13][1] == 175
+    assert all(rows[n][0] in (1, 2, 20) for n in range(1, 8))          # (what cases 1 .. 7 gave the column sum)
+    for n in range(8, 14):                                             # integer data: results far below 2^24
+        res = orc.op_value_and_grads(*orc.case_tensors(n, "int"), orc.OP_CASES[n][5], torch.float64)
+        assert max(float(v.abs().max()) for v in res.values() if v is not None) < 4e3, n
 
 
 def test_out_shape_rule():

@@ -11,7 +11,7 @@ import torch
 
 from tests import guard, rdn_oracle as orc
 from tests.guard_family import check_family_table, check_header_is_c99
-from tests.util import GOLD, gold
+from tests.util import GOLD, digest, gold
 
 NAMES = {"modet_convs2_ws_bytes", "modet_convs2_fwd", "modet_convs2_bwd_data", "modet_convs2_bwd_weight", "modet_cat_channels2_fwd",
          "modet_cat_channels2_bwd"}
@@ -84,6 +84,42 @@ def test_oracle_layer_runs_in_fp32_and_follows_the_padding_rule():
     xi, wi, bi, gi = orc.case_tensors(5, "int")
     ri = orc.op_value_and_grads(xi, wi, bi, gi, 0.0, torch.float64)
     assert all(torch.equal(v, v.round()) for v in ri.values())          # ReLU on integers: integer results
+
+
+def test_masked_share_of_every_case_is_below_the_cap():
+    """cases 1 .. 7 keep every cotangent (their tensors are pinned below); from case MASKED_FROM on the outputs within MASK_BELOW of
+    zero lose theirs: 1 of case 11's 6 600, about 1e-5 of the larger cases'"""
+    from tests import rcn_oracle
+    assert (orc.MASK_BELOW, orc.MASK_CAP) == (rcn_oracle.MASK_BELOW, rcn_oracle.MASK_CAP) and orc.MASK_CAP == 0.01
+    for n, case in orc.OP_CASES.items():
+        share = orc.masked_share(n)
+        assert 0.0 <= share <= orc.MASK_CAP, (n, share)
+        assert share == 0.0 or (case[4] is not None and n >= orc.MASKED_FROM), n
+        if n >= orc.MASKED_FROM and case[4] is not None:
+            x, w, b, gy = orc.case_tensors(n)
+            near = orc.conv_s2_cl(x.double(), w.double(), b.double(), case[4]).abs() < orc.MASK_BELOW
+            assert float(gy[near].abs().sum()) == 0.0 and float(near.double().mean()) == share, n
+
+
+def test_tensors_of_cases_1_to_7_are_what_they_always_were():
+    """goldens, guard files and the frozen yardstick of tests/test_gpu_convs2.py rest on these tensors: a checksum taken before
+    the case table grew and tensor construction moved into spec_tensors"""
+    assert digest(t for n in range(1, 8) for kind in ("randn", "int") for t in orc.case_tensors(n, kind)) == \
+        "19c4a1fba2ff79fa2ee2c1b303fb948a00b379bbff447a055f454dedd410e59e"
+
+
+def test_new_cases_launch_what_they_are_named_for():
+    """the arithmetic behind the comments of OP_CASES 8 .. 11: the weight gradient's row counts and the last split"""
+    rows = {}
+    for n, (B, (D, H, W), _, cout, _) in orc.OP_CASES.items():
+        Do, Ho, Wo = orc.out_shape(D, H, W)
+        N, V = B * Do * Ho * Wo, (256 if cout <= 64 else 512 if cout <= 128 else 1024)
+        rows[n] = (V, -(-N // V), N - (-(-N // V) - 1) * V)
+    assert {n: rows[n] for n in (8, 9, 10, 11)} == {8: (256, 6, 250), 9: (512, 2, 208), 10: (1024, 3, 112), 11: (256, 7, 114)}
+    assert all(rows[n][1] in (1, 3) for n in range(1, 8))              # (what cases 1 .. 7 gave the column sum)
+    for n in range(8, 12):                                             # integer data: results far below 2^24
+        res = orc.op_value_and_grads(*orc.case_tensors(n, "int"), orc.OP_CASES[n][4], torch.float64)
+        assert max(float(v.abs().max()) for v in res.values()) < 4e3, n
 
 
 def test_output_size_rule_for_odd_and_even_dimensions():

@@ -3,14 +3,22 @@ fp64 (tests/rdn_oracle.py: F.conv3d(stride=2, padding=1) + LeakyReLU, the refere
 the same layer makes in ATen fp32 on the CPU.
 
 THE RULE (tests/test_gpu_im2grid.py's and tests/test_gpu_vecint.py's): per quantity, HIP's error against fp64 is at most A = 4 times
-the LARGEST ATen-fp32 error of that quantity over the cases of this file.  An error is max|got - ref| / max|ref|.  Every measured
-figure goes to the parity report (tests.util.note_many) before it is asserted.
+the LARGEST ATen-fp32 error of that quantity over cases 1 .. 7 of this file (YARD_CASES: the yardstick is frozen to them, a later
+case cannot raise it).  A case from 8 on may use A times its OWN ATen-fp32 error instead where that is larger (case 10's d_w and
+d_b sum 2 160 voxels: ATen's own errors there, 1.9e-6 and 1.5e-6, are beyond what the small cases show).  An error is
+max|got - ref| / max|ref|.  Every measured figure, HIP's and ATen's, goes to the parity report (tests.util.note_many) before it is
+asserted.
 
 TILES.  The kernels are flat launches of 256 threads without a grid cap: the forward has one thread per (output voxel, 4 output
 channels), the data gradient one per (input voxel, 4 input channels), the weight gradient 256 (tap, 4 ci, 4 co) items per workgroup
-and one workgroup row per 256 output voxels.  Case 6 (9x17x33, 4 -> 8: 765 output and 5 049 input voxels) gives them 6, 20 and 3
-workgroups, the last one partial in each -- there are no per-axis tiles, so "a partial tile in every axis" is the partial last
-workgroup of a flat index whose three axes are all odd."""
+and one workgroup row per V = 256, 512 (Cout > 64) or 1024 (Cout > 128) output voxels; its S = ceil(N / V) rows are summed four
+at a time.  The 11 cases: 1 .. 7 are the network's shapes and the smallest ones (case 6, 9x17x33, 4 -> 8: 765 output and 5 049
+input voxels, gives the three kernels 6, 20 and 3 workgroups, the last one partial in each -- there are no per-axis tiles, so "a
+partial tile in every axis" is the partial last workgroup of a flat index whose three axes are all odd); S is 1 or 3 in all of them.
+8: Cin = 1 without an activation (convs2_bwd_data_kernel<1,false>, convs2_bwd_weight_kernel<1,false>), S = 6.  9: V = 512 with two
+rows, the last one of 208 voxels.  10: V = 1024 with three rows, the second across the batch boundary, the last one of 112 voxels.
+11: S = 7.  With tests/test_gpu_deconv.py's 5, 7 and 256 the column sum runs one round of four and a tail of 1, 2 and 3 rows, and
+64 rounds without a tail."""
 import functools
 
 import pytest
@@ -24,6 +32,8 @@ pytestmark = pytest.mark.gpu
 A = 4.0
 QUANTITIES = ("y", "d_x", "d_w", "d_b")
 CASES = tuple(sorted(orc.OP_CASES))
+YARD_CASES = (1, 2, 3, 4, 5, 6, 7)         # the yardstick's cases, frozen
+NEW_CASES = tuple(n for n in CASES if n not in YARD_CASES)
 
 
 @functools.lru_cache(maxsize=None)
@@ -35,15 +45,29 @@ def oracle(n, kind="randn"):
 
 @functools.lru_cache(maxsize=None)
 def aten_yardstick():
-    """quantity -> the largest ATen-fp32 (CPU) error over the file's cases"""
+    """quantity -> the largest ATen-fp32 (CPU) error over YARD_CASES"""
     worst = {q: 0.0 for q in QUANTITIES}
-    for n in CASES:
+    for n in YARD_CASES:
         t, ref = oracle(n)
         got = orc.op_value_and_grads(*t, orc.OP_CASES[n][4], torch.float32)
         for q in QUANTITIES:
             worst[q] = max(worst[q], rel_err(got[q], ref[q]))
     note_many({"convs2.aten_f32.%s" % q: v for q, v in worst.items()})
     return worst
+
+
+@functools.lru_cache(maxsize=None)
+def allowed(n):
+    """quantity -> the error case n may show: A x the frozen yardstick, for a case from 8 on A x its own ATen-fp32 (CPU) error if
+    that is larger (noted as convs2.aten_f32[case<n>].<quantity>)"""
+    yard = aten_yardstick()
+    if n in YARD_CASES:
+        return {q: A * yard[q] for q in QUANTITIES}
+    t, ref = oracle(n)
+    got = orc.op_value_and_grads(*t, orc.OP_CASES[n][4], torch.float32)
+    own = {q: rel_err(got[q], ref[q]) for q in QUANTITIES}
+    note_many({"convs2.aten_f32[case%d].%s" % (n, q): v for q, v in own.items()})
+    return {q: A * max(yard[q], own[q]) for q in QUANTITIES}
 
 
 def hip(x, w, b, gy, slope, x_grad=True):
@@ -57,19 +81,20 @@ def hip(x, w, b, gy, slope, x_grad=True):
 
 @pytest.mark.parametrize("n", CASES)
 def test_layer_against_fp64_in_units_of_aten_fp32(n):
-    (t, ref), yard = oracle(n), aten_yardstick()
+    (t, ref), bound = oracle(n), allowed(n)
     got = hip(*t, orc.OP_CASES[n][4])
     errs = {q: rel_err(got[q], ref[q]) for q in QUANTITIES}
     note_many({"convs2[case%d].%s.e_hip" % (n, q): e for q, e in errs.items()})
     for q in QUANTITIES:
         assert got[q].shape == ref[q].shape
-        assert errs[q] <= A * yard[q], "case %d %s: e_hip %.3e, largest ATen fp32 error %.3e (A = %g)" % (n, q, errs[q], yard[q], A)
+        assert errs[q] <= bound[q], "case %d %s: e_hip %.3e, A x ATen fp32's error %.3e (A = %g)" % (n, q, errs[q], bound[q], A)
 
 
-@pytest.mark.parametrize("n", (1, 2, 5, 6))
+@pytest.mark.parametrize("n", (1, 2, 5, 6) + NEW_CASES)
 def test_integer_data_equals_fp64_bit_for_bit(n):
-    """x, w, b, d_y integers in [-3, 3]: every product and sum is exactly representable, so whatever the summation order the four
-    results ARE the fp64 ones (the slope enters once, as fl(P + slope * Q) of two exact integer sums)"""
+    """x, w, b, d_y integers in [-3, 3]: every product and sum is exactly representable (at most 27 * 256 * 9 in case 10's data
+    gradient and 2 160 * 9 in its weight gradient, all below 2^24), so whatever the summation order the four results ARE the fp64
+    ones (the slope enters once, as fl(P + slope * Q) of two exact integer sums)"""
     t, ref = oracle(n, "int")
     got = hip(*t, orc.OP_CASES[n][4])
     for q in QUANTITIES:
@@ -77,7 +102,7 @@ def test_integer_data_equals_fp64_bit_for_bit(n):
         assert float(ref[q].abs().max()) > 0
 
 
-@pytest.mark.parametrize("n", (2, 5, 6))
+@pytest.mark.parametrize("n", (2, 5, 6, 8))
 def test_delta_weights_pick_single_input_voxels(n):
     """centre tap + identity channels: y[o] == x[2o], d_x == d_y at even indices and 0 elsewhere; tap (0,0,0): y[o] == x[2o - 1],
     0 where that is padding"""
@@ -106,7 +131,7 @@ def test_delta_weights_pick_single_input_voxels(n):
         assert torch.equal(dx.cpu(), wdx), (n, tap)
 
 
-@pytest.mark.parametrize("n", (1, 5, 6))
+@pytest.mark.parametrize("n", (1, 5, 6, 10))
 def test_two_runs_are_bit_identical_and_a_batch_equals_its_samples(n):
     t = orc.case_tensors(n)
     B, slope = orc.OP_CASES[n][0], orc.OP_CASES[n][4]

@@ -4,7 +4,9 @@ between guard bands (tests/guard.py), every workspace is exactly modet_convs2_ws
 poisoned, and the library is reached through a recording proxy over the new table.  Per case: no band is damaged, every result is
 finite, the results equal an unguarded run bit for bit, and a second guarded run with 0x00 instead of 0xFF bands and poison gives
 the same bits.  The shapes: cases 1, 3, 4 and 6 of tests/test_gpu_convs2.py (odd axes with high-end padding and Cin = 1, one
-output voxel at 64 -> 128, a single input voxel without activation, several workgroups with a partial last one)."""
+output voxel at 64 -> 128, a single input voxel without activation, several workgroups with a partial last one), case 8 through
+the ABI (Cin = 1 without an activation, six partial rows in an exact workspace) and case 9 through the wrapper (two rows of 512
+voxels, the last one partial)."""
 import pytest
 import torch
 
@@ -55,6 +57,8 @@ CASES = {}
 for _n in (1, 3, 4, 6):
     CASES["abi[case%d]" % _n] = S.abi_case(_n)
     CASES["ops[case%d]" % _n] = S.ops_case(_n)
+CASES["abi[case8]"] = S.abi_case(8)
+CASES["ops[case9]"] = S.ops_case(9)
 CASES["abi[case6,no bias]"] = S.abi_case(6, bias=False)
 CASES["ops[case1,no bias]"] = S.ops_case(1, bias=False)
 CASES["cat abi[3x5x7,8+16]"] = cat_abi_case((1, 3, 5, 7), 8, 16)

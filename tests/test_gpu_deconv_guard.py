@@ -4,7 +4,9 @@ bands (tests/guard.py), every workspace is exactly modet_deconv4s2_ws_bytes(...,
 and the library is reached through a recording proxy over the new table.  Per case: no band is damaged, every result is finite,
 the results equal an unguarded run bit for bit, and a second guarded run with 0x00 instead of 0xFF bands and poison gives the same
 bits.  The shapes: cases 1, 3, 4 and 6 of tests/test_gpu_deconv.py (a single input voxel, 3 -> 3 channels with scalar tails on both
-sides, the 259-channel tail of x / d_x beside 16-byte loads of y, several tiles with a partial one in every axis)."""
+sides, the 259-channel tail of x / d_x beside 16-byte loads of y, several tiles with a partial one in every axis) and cases 9, 10
+and 12 (an activation with a Cout tail, so that y and d_y are read channel by channel up to the band, beside 16-byte rows of x at
+20 -> 6 and 24 -> 13; the 35-channel tail of x beside 16-byte rows of y, the last row of workgroups partly empty)."""
 import pytest
 import torch
 
@@ -21,6 +23,9 @@ S = StridedLayer(orc, "deconv4s2", "conv_transpose3d_k4s2", has_bias=lambda n: o
 
 CASES = {}
 for _n in (1, 3, 4, 6):
+    CASES["abi[case%d]" % _n] = S.abi_case(_n)
+    CASES["ops[case%d]" % _n] = S.ops_case(_n)
+for _n in (9, 10, 12):
     CASES["abi[case%d]" % _n] = S.abi_case(_n)
     CASES["ops[case%d]" % _n] = S.ops_case(_n)
 CASES["abi[case6,no bias]"] = S.abi_case(6, bias=False)

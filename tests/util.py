@@ -1,4 +1,5 @@
 """helpers shared by the parity tests"""
+import hashlib
 import json
 import os
 
@@ -10,6 +11,15 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 def gold(name):
     return np.load(os.path.join(GOLD, name))
+
+
+def digest(tensors):
+    """sha256 over the bytes of the host tensors given, in order (None entries are skipped): pins seeded test data bit for bit"""
+    h = hashlib.sha256()
+    for t in tensors:
+        if t is not None:
+            h.update(t.contiguous().numpy().tobytes())
+    return h.hexdigest()
 
 
 def dev():
