@@ -201,6 +201,20 @@ FAMILIES = {
         "modet_deconv4s2_bwd_data": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, I, F, P]),
         "modet_deconv4s2_bwd_weight": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, I, I, F, P]),
     }),
+    "pcnet": (_header("modet_hip_pcnet.h"), {
+        "modet_pcnet_upsample_fwd": (I, [P, P, I, I, I, I, I, I, I, P]),
+        "modet_pcnet_upsample_bwd": (I, [P, P, I, I, I, I, I, I, I, P]),
+        "modet_pcnet_dfi_gate_fwd": (I, [P, P, P, I64, I, P]),
+        "modet_pcnet_dfi_gate_bwd": (I, [P, P, P, P, P, I64, I, P]),
+        "modet_pcnet_nff_ws_bytes": (SZ, [I, I64, I, I]),
+        "modet_pcnet_nff_pool": (I, [P, P, P, P, P, P, P, P, SZ, I, I64, I, P]),
+        "modet_pcnet_nff_gate_fwd": (I, [P, P, P, P, P, I, I, P]),
+        "modet_pcnet_nff_gate_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, SZ, I, I, P]),
+        "modet_pcnet_nff_apply_fwd": (I, [P, P, P, P, P, P, I, I64, I, P]),
+        "modet_pcnet_nff_apply_bwd_gate": (I, [P, P, P, P, P, P, P, SZ, I, I64, I, P]),
+        "modet_pcnet_nff_apply_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I64, I, P]),
+        "modet_pcnet_add": (I, [P, P, P, I64, P]),
+    }),
 }
 # The names a family's entry had before the registry.  Nothing in this tree uses them; they stay because the previous revision's
 # test files, which every change is also run against, reach the library through them (about 95 test ids).  Views of FAMILIES:

@@ -40,7 +40,9 @@ int modet_hip_version(void) { return 447;
               one fixed-order fp64 column sum) and the two-tensor channel concatenation
      0.4.4.7: + modet_deconv4s2_ws_bytes, modet_deconv4s2_fwd, modet_deconv4s2_bwd_data, modet_deconv4s2_bwd_weight
               (include/modet_hip_deconv.h): the 4x4x4 transposed convolution with stride 2 and padding 1 and a fused
-              LeakyReLU(slope) of the RCN / VTN and PCNet decoders, any channel count up to 1024, on LDS-staged 3-D tiles */ }
+              LeakyReLU(slope) of the RCN / VTN and PCNet decoders, any channel count up to 1024, on LDS-staged 3-D tiles
+     0.4.4.8: + the twelve modet_pcnet_* entry points (include/modet_hip_pcnet.h): trilinear upsampling by 2 / 4 / 8 into a slice of
+              a wider row, DFI's gated sum, the NFF tail (pool, gate, apply and their backward passes) and the residual sum */ }
 
 const char* modet_hip_strerror(int code) {
   switch (code) {

@@ -7,6 +7,7 @@ fraction of voxels with non-positive Jacobian determinant; with --surface also H
     python -m smilecode_amd.infer --synthetic 2 --img-size 32,32,32 --surface  # + one HD95 / ASSD line per pair and a summary
     python -m smilecode_amd.infer --model rdn --channels 16 --levels 1,1,1,1 --model-dir experiments/<run>/   # an RDN checkpoint
     python -m smilecode_amd.infer --model rcn --channels 8 --cascades 10 --img-size 192,192,192 --model-dir experiments/<run>/   # an RCN checkpoint
+    python -m smilecode_amd.infer --model pcnet --channels 16 --model-dir experiments/<run>/   # a PCNet checkpoint
 """
 from __future__ import annotations
 
@@ -32,7 +33,7 @@ def make_parser():
     ap.add_argument("--surface", action="store_true",
                     help="also report HD95 and ASSD (voxels) of the warped and the raw labels, computed on the GPU")
     ap.add_argument("--model", choices=MODELS, default="modet", help="the network the checkpoint was trained with (train --model)")
-    ap.add_argument("--channels", type=int, default=16, help="--model rdn / rcn: channels of the first encoder layer, as trained")
+    ap.add_argument("--channels", type=int, default=16, help="--model rdn / rcn / pcnet: channels of the first encoder layer, as trained")
     ap.add_argument("--cascades", type=int, default=10, help="--model rcn: number of cascaded VTNs, as trained")
     ap.add_argument("--levels", default="1,1,1,1", help="--model rdn: Estimator passes per level a,b,c,d, finest level first, as trained")
     return ap

@@ -1190,6 +1190,254 @@ class RCN(nn.Module):
         return (moved, flow, *subs) if subflows else (moved, flow)
 
 
+class ResBlock(nn.Module):
+    """PCNet's VoxRes block ("Baseline methods/PCnet/models.py":168-186): conv(LeakyReLU(InstanceNorm(x))) + x, then InstanceNorm +
+    LeakyReLU(0.1).  ``block`` keeps nn.Sequential's indices (2 is the convolution); channels-last in/out.  The first norm exists
+    only inside the convolution's kernels where they can apply it (ops.lazy_instnorm_conv3d), the sum is one kernel."""
+
+    def __init__(self, channel):
+        super().__init__()
+        self.block = nn.ModuleList([nn.Identity(), nn.Identity(), _Conv3dParams(channel, channel)])
+
+    def forward(self, x):
+        z, _ = ops.lazy_instnorm_conv3d(x, None, self.block[2].weight, self.block[2].bias, want_stats=False)
+        return ops.instnorm_lrelu(ops.residual_add(z, x))
+
+
+class EncoderRes(nn.Module):
+    """PCNet's encoder (":189-221): a ConvInsBlock at full resolution, then three times a stride-2 convolution (no activation) and
+    a ResBlock; c, 2c, 4c, 8c channels at 1, 1/2, 1/4, 1/8.  ``convN`` keeps nn.Sequential's indices 0 and 1."""
+
+    def __init__(self, in_channel=1, first_out_channel=16):
+        super().__init__()
+        c = first_out_channel
+        self.conv0 = ConvInsBlock(in_channel, c)
+        self.conv1 = nn.ModuleList([_Conv3dParams(c, 2 * c), ResBlock(2 * c)])
+        self.conv2 = nn.ModuleList([_Conv3dParams(2 * c, 4 * c), ResBlock(4 * c)])
+        self.conv3 = nn.ModuleList([_Conv3dParams(4 * c, 8 * c), ResBlock(8 * c)])
+
+    def forward(self, x):
+        outs = [self.conv0(x)]
+        for conv, res in (self.conv1, self.conv2, self.conv3):
+            outs.append(res(ops.conv3d_s2(outs[-1], conv.weight, conv.bias, None)))
+        return outs
+
+
+class UpConvInsBlock(nn.Module):
+    """PCNet's UpConvBlock (":154-166): nn.ConvTranspose3d(cin, cout, 4, stride=2, padding=1) with bias, InstanceNorm, LeakyReLU(0.1)"""
+
+    def __init__(self, in_channels, out_channels, kernel_size=4, stride=2):
+        super().__init__()
+        _k4s2_only("UpConvBlock", kernel_size, stride)
+        self.upconv = _ConvTranspose3dParams(in_channels, out_channels, bias=True)
+
+    def forward(self, x):
+        return ops.instnorm_lrelu(ops.conv_transpose3d_k4s2(x, self.upconv.weight, self.upconv.bias, None))
+
+
+class DFIBlock(nn.Module):
+    """PCNet's deformation-field integration (":225-270): the n = 5 - level predictions so far, upsampled to this level's grid by
+    2^n .. 2 straight into the channels of one buffer (ops.upsample_pow2), two ConvInsBlocks 3n -> 16n -> 16n, n weight
+    convolutions 16n -> 3 whose logits are concatenated, the gated sum (ops.dfi_gate) and VecInt.  The
+    reference hard-codes channel = 16 whatever the network's width; state-dict keys ``conv.{0,1}.main.*``,
+    ``weight_conv.<i>.0.*`` (index 1 is the Sigmoid) and ``integrate.transformer.grid`` as ModeT handles it."""
+
+    def __init__(self, inshape, level, steps=7, channel=16, legacy_grid_buffers=False):
+        super().__init__()
+        c, n = channel, 5 - level
+        self.list_num = n
+        self.conv = nn.ModuleList([ConvInsBlock(3 * n, c * n), ConvInsBlock(c * n, c * n)])
+        self.weight_conv = nn.ModuleList([nn.ModuleList([_Conv3dParams(c * n, 3), nn.Identity()]) for _ in range(n)])
+        self.integrate = VecInt(inshape, steps, legacy_grid_buffers=legacy_grid_buffers)
+
+    def forward(self, prediction_list):
+        n = self.list_num
+        if len(prediction_list) != n:
+            raise RuntimeError(f"DFIBlock: {len(prediction_list)} predictions for a block built for {n}")
+        B, d, h, w, _ = prediction_list[0].shape
+        f = 2 ** n
+        x = torch.empty((B, f * d, f * h, f * w, 3 * n), dtype=torch.float32, device=prediction_list[0].device)
+        for i, p in enumerate(prediction_list):
+            x = ops.upsample_pow2(p, 2 ** (n - i), x, 3 * i)
+        # the fields are not bounded like a normalised activation: no x_act promise for the first convolution
+        feat = _two_blocks(x, self.conv[0], self.conv[1], x_act=False)
+        # one launch per weight convolution, on the parameters themselves: a step packs every convolution weight up front from the
+        # address it had in the step before (ops.StepContext), so a concatenated temporary weight must not reach a convolution
+        logits = None
+        for m in self.weight_conv:
+            lg = ops.conv3d(feat, m[0].weight, m[0].bias, False, x_act=True)
+            logits = lg if logits is None else ops.cat_channels(logits, lg)
+        return self.integrate.forward_cl(ops.dfi_gate(x, logits))
+
+
+class _LinearNoBias(nn.Module):
+    """parameter holder with nn.Linear(cin, cout, bias=False)'s name, shape and default init"""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+
+
+class ChannelAttention(nn.Module):
+    """parameters of PCNet's ChannelAttention (":272-292): ``fc.0`` (channel // 8, channel) and ``fc.2`` (channel, channel // 8);
+    the pooling, the two layers and the sigmoid run inside ops.nff_fuse"""
+
+    def __init__(self, channel, reduction=8):
+        super().__init__()
+        if reduction != 8:
+            raise RuntimeError(f"ChannelAttention: reduction = {reduction}: the gate kernels are built for the reference's 8")
+        self.fc = nn.ModuleList([_LinearNoBias(channel, channel // reduction), nn.Identity(), _LinearNoBias(channel // reduction, channel)])
+
+
+class NFFBlock(nn.Module):
+    """PCNet's feature fusion (":294-322) over three maps of channel / 3 channels each: two ConvInsBlocks and a convolution to 3
+    logits over their concatenation, then the fused tail (ops.nff_fuse: voxel softmax, weighted concatenation, global average and
+    max pooling, the two-layer gate, the rescale).  ``weight_conv`` keeps nn.Sequential's indices (1 is the Softmax)."""
+
+    def __init__(self, channel):
+        super().__init__()
+        c = channel
+        self.conv = nn.ModuleList([ConvInsBlock(c, c), ConvInsBlock(c, c)])
+        self.weight_conv = nn.ModuleList([_Conv3dParams(c, 3), nn.Identity()])
+        self.channel_attention = ChannelAttention(c)
+
+    def forward(self, float_fm, fixed_fm, decon_fm):
+        cat = ops.cat_channels(ops.cat_channels(float_fm, fixed_fm), decon_fm)
+        feat = _two_blocks(cat, self.conv[0], self.conv[1])
+        logits = ops.conv3d(feat, self.weight_conv[0].weight, self.weight_conv[0].bias, False, x_act=True)
+        fc = self.channel_attention.fc
+        return ops.nff_fuse(float_fm, fixed_fm, decon_fm, logits, fc[0].weight, fc[2].weight)
+
+
+PCNET_MAX_STRIDE1_WIDTH = 256       # the widest stride-1 convolution is the bottleneck's 16c -> 8c (csrc/conv3d.hip: up to 256 channels)
+
+
+def pcnet_unsupported_config(in_channel=1, channels=16, act_dtype=torch.float32, overlap_allreduce=False):
+    """None if every kernel on PCNet's path accepts the configuration, else a message naming the argument.  The library is asked
+    for the stride-2, transposed and NFF kernels' limits; the stride-1 limit is restated, as rdn_unsupported_config does."""
+    if act_dtype != torch.float32:
+        return f"act_dtype = {act_dtype}: the stride-2, transposed-convolution and fusion kernels are fp32 only (bf16 storage is ModeT's)"
+    if overlap_allreduce:
+        return "overlap_allreduce = True: the overlapped all-reduce cuts the backward at ModeT's three bucket boundaries, which PCNet does not have"
+    if isinstance(in_channel, bool) or int(in_channel) != in_channel or in_channel < 1:
+        return f"in_channel = {in_channel}: a positive integer"
+    if isinstance(channels, bool) or int(channels) != channels or channels < 1:
+        return f"channels = {channels}: a positive integer"
+    L, c = ops._L(), channels
+    for cin, cout in [(c, 2 * c), (2 * c, 4 * c), (4 * c, 8 * c)]:
+        if L.modet_convs2_ws_bytes(1, 16, 16, 16, cin, cout, 0) == 0:
+            return (f"channels = {channels}: the encoder's stride-2 layer {cin} -> {cout} is refused (the convs2 kernels take 1 or a "
+                    f"multiple of 4 input channels and a multiple of 4 output channels, up to {ops.CONVS2_MAX_CHANNELS})")
+    for cin, cout in [(8 * c, 4 * c), (12 * c, 2 * c), (6 * c, c)]:
+        if L.modet_deconv4s2_ws_bytes(1, 2, 2, 2, cin, cout, 0) == 0:
+            return f"channels = {channels}: the decoder's transposed convolution {cin} -> {cout} is refused by the deconv kernels"
+    for C in (4 * c, 2 * c, c):
+        if L.modet_pcnet_nff_ws_bytes(1, 8, C, 0) == 0:
+            return (f"channels = {channels}: an NFF block fuses three maps of {C} channels; the fusion kernels take a multiple of 4 "
+                    f"from 4 to {ops._lib_limit('MODET_PCNET_MAX_C')}")
+    if 16 * c > PCNET_MAX_STRIDE1_WIDTH:
+        return (f"channels = {channels}: the bottleneck convolves {16 * c} -> {8 * c} channels; the stride-1 kernels take up to "
+                f"{PCNET_MAX_STRIDE1_WIDTH}, so channels is a multiple of 4 from 4 to {PCNET_MAX_STRIDE1_WIDTH // 16}")
+    return None
+
+
+class PCNet(nn.Module):
+    """The PCNet baseline ("Baseline methods/PCnet/models.py":324-428): two encoders with separate weights, a bottleneck over
+    [fixed; moving] at 1/8, and three decoder levels that each predict a field (reg_conv*), upsample the features (upconv*),
+    integrate all predictions so far into a warping field (dfi_*), warp the moving features by it and fuse [fixed; warped; upconv]
+    (nff_*); the output flow composes the finest warping field with the integrated last prediction.  Same constructor arguments,
+    attribute names and state-dict keys as the reference (the ``*.grid`` buffers as ModeT handles them, ``legacy_grid_buffers``).
+    ``forward(moving, fixed)`` returns ``(y_moved, flow)``.  fp32 only."""
+
+    stage_buckets = False       # engine.Trainer: the three-stage bucket cut of the overlapped all-reduce is ModeT's
+
+    def __init__(self, inshape=(160, 192, 160), flow_multiplier=1., in_channel=1, channels=16, legacy_grid_buffers=False,
+                 act_dtype=torch.float32, overlap_allreduce=False):
+        super().__init__()
+        why = pcnet_unsupported_config(in_channel, channels, act_dtype, overlap_allreduce)
+        if why is not None:
+            raise RuntimeError("PCNet: " + why)
+        why = self.unsupported_shape(inshape)
+        if why is not None:
+            raise RuntimeError("PCNet: inshape: " + why)
+        self.flow_multiplier = flow_multiplier
+        self.channels = channels
+        self.step = 7
+        self.inshape = tuple(int(s) for s in inshape)
+        self.act_dtype = act_dtype
+        c, lg = channels, legacy_grid_buffers
+        shape = lambda k: [s // k for s in self.inshape]          # noqa: E731
+        self.encoder_float = EncoderRes(in_channel=in_channel, first_out_channel=c)
+        self.encoder_fixed = EncoderRes(in_channel=in_channel, first_out_channel=c)
+        self.conv_bottleNeck = nn.ModuleList([ConvInsBlock(16 * c, 8 * c), ConvInsBlock(8 * c, 8 * c)])
+        self.reg_conv3 = _Conv3dParams(2 * 4 * c, 3)
+        self.upconv2 = UpConvInsBlock(8 * c, 4 * c, 4, 2)
+        self.dfi_2 = DFIBlock(shape(4), 4, legacy_grid_buffers=lg)
+        self.transformer_2 = SpatialTransformer(shape(4), legacy_grid_buffers=lg)
+        self.nff_2 = NFFBlock(3 * 4 * c)
+        self.reg_conv2 = _Conv3dParams(3 * 4 * c, 3)
+        self.upconv1 = UpConvInsBlock(3 * 4 * c, 2 * c, 4, 2)
+        self.dfi_1 = DFIBlock(shape(2), 3, legacy_grid_buffers=lg)
+        self.transformer_1 = SpatialTransformer(shape(2), legacy_grid_buffers=lg)
+        self.nff_1 = NFFBlock(3 * 2 * c)
+        self.reg_conv1 = _Conv3dParams(3 * 2 * c, 3)
+        self.upconv0 = UpConvInsBlock(3 * 2 * c, c, 4, 2)
+        self.dfi_0 = DFIBlock(shape(1), 2, legacy_grid_buffers=lg)
+        self.transformer_0 = SpatialTransformer(shape(1), legacy_grid_buffers=lg)
+        self.nff_0 = NFFBlock(3 * c)
+        self.reg_conv0 = nn.ModuleList([_Conv3dParams(3 * c, c), _Conv3dParams(c, 3)])
+        self.integrate = VecInt(self.inshape, legacy_grid_buffers=lg)
+        self.transformer_out = SpatialTransformer(self.inshape, legacy_grid_buffers=lg)
+
+    @staticmethod
+    def unsupported_shape(shape):
+        """None, or why a (D,H,W) volume cannot go through the three stride-2 levels and back"""
+        shape = tuple(shape)
+        if len(shape) != 3:
+            return f"(D, H, W) expected, got {shape}"
+        if any(int(v) % 8 != 0 for v in shape):
+            return f"every spatial dimension must be a multiple of 8 (three stride-2 layers, then x2 transposed convolutions back), got {shape}"
+        if any(int(v) < 16 for v in shape):
+            return (f"every spatial dimension must be at least 16 (the coarsest grid needs 2 voxels per axis: trilinear upsampling "
+                    f"with align_corners=True has no scale for an axis of 1), got {shape}")
+        return None
+
+    def forward(self, moving, fixed):
+        """(y_moved (B,1,D,H,W), flow (B,3,D,H,W))"""
+        return tuple(ops.to_ncdhw(t) for t in self.forward_cl(moving, fixed))
+
+    def forward_cl(self, moving, fixed):
+        """``forward`` with the results channels-last, as the kernels wrote them: y_moved (B,D,H,W,1), flow (B,D,H,W,3)"""
+        if moving.shape != fixed.shape or moving.dim() != 5:
+            raise RuntimeError("PCNet.forward expects two (B,C,D,H,W) volumes of the same shape")
+        why = self.unsupported_shape(moving.shape[2:])
+        if why is not None:
+            raise RuntimeError("PCNet.forward: " + why)
+        mov_cl = ops.to_channels_last(moving.contiguous())
+        fix_cl = ops.to_channels_last(fixed.contiguous())
+        with ops.trace_range("encoder"):
+            M = self.encoder_float(mov_cl)
+            Fx = self.encoder_fixed(fix_cl)
+        with ops.trace_range("bottleneck"):
+            feat = _two_blocks(ops.cat_channels(Fx[3], M[3]), self.conv_bottleNeck[0], self.conv_bottleNeck[1])
+        preds, field = [], None
+        for lvl in (2, 1, 0):
+            with ops.trace_range("level%d" % lvl):
+                reg = getattr(self, "reg_conv%d" % (lvl + 1))
+                preds.append(ops.conv3d(feat, reg.weight, reg.bias, False, x_act=True))
+                deconv = getattr(self, "upconv%d" % lvl)(feat)
+                field = getattr(self, "dfi_%d" % lvl)(preds)
+                warped = getattr(self, "transformer_%d" % lvl).forward_cl(M[lvl], field)
+                feat = getattr(self, "nff_%d" % lvl)(Fx[lvl], warped, deconv)
+        with ops.trace_range("output"):
+            pred0 = ops.conv3d(feat, self.reg_conv0[0].weight, self.reg_conv0[0].bias, False, x_act=True)
+            pred0 = ops.conv3d(pred0, self.reg_conv0[1].weight, self.reg_conv0[1].bias, False)
+            pred0 = self.integrate.forward_cl(pred0)
+            flow = self.transformer_out.forward_cl(field, pred0, add_flow=True)
+            return ops.warp_tee(mov_cl, flow)       # (the flow's other consumer: the caller, Grad3d in training)
+
+
 def load_numpy_weights(model: nn.Module, weights) -> None:
     """copy a name -> ndarray dict (smilecode_amd.synth.make_weights) into the model's parameters"""
     params = dict(model.named_parameters())

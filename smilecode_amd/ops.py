@@ -1868,6 +1868,223 @@ def cwm_tail(x, logits):
     return _CwmTail.apply(x, logits)
 
 
+# ---- the PCNet family (include/modet_hip_pcnet.h): upsampling by 2 / 4 / 8 into a slice of a row, DFI's gated sum, the NFF tail
+_UP_FACTORS, _UP_ROWS = (2, 4, 8), (3, 6, 9)
+
+
+def _up_args(op, x, f, out, offset):
+    _chk(x, out)
+    _rank5(op, "x", x)
+    B, d, h, w, C = x.shape
+    if C != 3:
+        raise RuntimeError(f"{op}: x {tuple(x.shape)} must have 3 channels (a displacement field)")
+    if f not in _UP_FACTORS:
+        raise RuntimeError(f"{op}: f must be one of {_UP_FACTORS}, got {f!r}")
+    if B < 1 or min(d, h, w) < 2:
+        raise RuntimeError(f"{op}: x {tuple(x.shape)} needs a batch and at least 2 voxels along every axis (align_corners=True has "
+                           "no scale for an axis of 1)")
+    ld = 3 if out is None else (out.shape[-1] if out.dim() == 5 else -1)
+    if out is not None:
+        if ld not in _UP_ROWS:
+            raise RuntimeError(f"{op}: out {tuple(out.shape)} must be channels-last with 3, 6 or 9 channels")
+        _same_shape(op, "out", out, (B, f * d, f * h, f * w, ld), f"x {tuple(x.shape)} upsampled by {f}")
+    elif offset != 0:
+        raise RuntimeError(f"{op}: offset {offset!r} needs an out tensor to index")
+    if not isinstance(offset, int) or offset < 0 or offset + 3 > ld:
+        raise RuntimeError(f"{op}: offset {offset!r} does not leave 3 channels in a row of {ld}")
+    if B * d * h * w * f ** 3 * ld >= 2 ** 31:
+        raise RuntimeError(f"{op}: the result of x {tuple(x.shape)} upsampled by {f} has 2^31 elements or more (the kernels' limit)")
+    return B, d, h, w, ld
+
+
+class _UpsamplePow2(Function):
+    """out is written in place in its channels [offset, offset + 3) and returned: autograd sees a fresh view of it per call, so
+    the three upsamplings of a DFI block chain through the one buffer and each backward reads its own slice of the gradient"""
+
+    @staticmethod
+    def forward(ctx, x, f, out, offset):
+        B, d, h, w, ld = _up_args("upsample_pow2", x, f, out, offset)
+        y = out if out is not None else torch.empty((B, f * d, f * h, f * w, 3), dtype=torch.float32, device=x.device)
+        nfine = B * d * h * w * f ** 3
+        with _Guard(x, f"upsample_pow2_fwd[x{f}]", 3.0 * 14.0 * nfine, 4.0 * (x.numel() + 3.0 * nfine)):
+            _call(_L().modet_pcnet_upsample_fwd, _p(x), _p(y), B, d, h, w, f, ld, offset, _stream())
+        if out is not None:
+            ctx.mark_dirty(out)
+        ctx.dims = (B, d, h, w, f, ld, offset)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, d, h, w, f, ld, offset = ctx.dims
+        dy = dy.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((B, d, h, w, 3), dtype=torch.float32, device=dy.device)
+            nfine = B * d * h * w * f ** 3
+            with _Guard(dy, f"upsample_pow2_bwd[x{f}]", 8.0 * 6.0 * nfine, 4.0 * (dx.numel() + 3.0 * nfine)):
+                _call(_L().modet_pcnet_upsample_bwd, _p(dy), _p(dx), B, d, h, w, f, ld, offset, _stream())
+        # the rows' other channels belong to the calls before this one: their gradient passes through; this call's slice was overwritten
+        dprev = None
+        if ctx.needs_input_grad[2]:
+            dprev = torch.empty_like(dy)
+            dprev.copy_(dy)
+            dprev[..., offset:offset + 3] = 0
+        return dx, None, dprev, None
+
+
+def upsample_pow2(x, f, out=None, offset=0):
+    """nn.Upsample(scale_factor=f, mode='trilinear', align_corners=True) of a channels-last 3-channel field, f in (2, 4, 8):
+    DFIBlock.upsample ("Baseline methods/PCnet/models.py":247-256).  With ``out`` (B,fd,fh,fw,ld), ld in (3, 6, 9), the result is
+    written into channels [offset, offset + 3) of it and ``out`` is returned (the torch.cat of DFIBlock.forward without a
+    concatenation kernel); the other channels are left untouched."""
+    return _UpsamplePow2.apply(x, f, out, offset)
+
+
+class _DfiGate(Function):
+    @staticmethod
+    def forward(ctx, x, logits):
+        _chk(x, logits)
+        if x.dim() < 2 or x.shape[-1] not in (3, 6, 9):
+            raise RuntimeError(f"dfi_gate: x {tuple(x.shape)} must end in 3, 6 or 9 channels (n fields of 3)")
+        _same_shape("dfi_gate", "logits", logits, tuple(x.shape), "x")
+        n = x.shape[-1] // 3
+        N = x.numel() // (3 * n)
+        if N < 1:
+            raise RuntimeError(f"dfi_gate: x {tuple(x.shape)} is empty")
+        out = torch.empty(tuple(x.shape[:-1]) + (3,), dtype=torch.float32, device=x.device)
+        with _Guard(x, f"dfi_gate_fwd[n{n}]", 8.0 * x.numel(), 4.0 * (2 * x.numel() + out.numel())):
+            _call(_L().modet_pcnet_dfi_gate_fwd, _p(x), _p(logits), _p(out), N, n, _stream())
+        ctx.save_for_backward(x, logits)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, logits = ctx.saved_tensors
+        dout = dout.contiguous()
+        n = x.shape[-1] // 3
+        N = x.numel() // (3 * n)
+        dx, dl = torch.empty_like(x), torch.empty_like(logits)
+        with _Guard(x, f"dfi_gate_bwd[n{n}]", 12.0 * x.numel(), 4.0 * (4 * x.numel() + dout.numel())):
+            _call(_L().modet_pcnet_dfi_gate_bwd, _p(x), _p(logits), _p(dout), _p(dx), _p(dl), N, n, _stream())
+        return dx, dl
+
+
+def dfi_gate(x, logits):
+    """sum_i x[..., 3i:3i+3] * sigmoid(logits[..., 3i:3i+3]) over the n = C / 3 fields of x (..., 3n), n in (1, 2, 3): the weighted
+    sum of DFIBlock.forward ("Baseline methods/PCnet/models.py":261-267) in one pass; the backward recomputes the sigmoid"""
+    return _DfiGate.apply(x, logits)
+
+
+def _nff_args(op, t0, t1, t2, logits, W1, W2):
+    _chk(t0, t1, t2, logits, W1, W2)
+    _rank5(op, "t0", t0)
+    B, D, H, W, C = t0.shape
+    _same_shape(op, "t1", t1, tuple(t0.shape), "t0")
+    _same_shape(op, "t2", t2, tuple(t0.shape), "t0")
+    _same_shape(op, "logits", logits, (B, D, H, W, 3), f"t0 {tuple(t0.shape)}: one logit per map and voxel")
+    V = D * H * W
+    if B < 1 or V < 1:
+        raise RuntimeError(f"{op}: t0 {tuple(t0.shape)} is empty")
+    if _L().modet_pcnet_nff_ws_bytes(B, V, C, 0) == 0:
+        raise RuntimeError(f"{op}: t0 {tuple(t0.shape)}: the kernels take a channel count that is a multiple of 4 from 4 to "
+                           f"{_lib_limit('MODET_PCNET_MAX_C')}, up to 65535 samples and fewer than 2^31 voxels per sample")
+    _same_shape(op, "W1", W1, (3 * C // 8, 3 * C), f"t0 {tuple(t0.shape)}: (3C // 8, 3C)")
+    _same_shape(op, "W2", W2, (3 * C, 3 * C // 8), f"t0 {tuple(t0.shape)}: (3C, 3C // 8)")
+    return B, V, C
+
+
+def _lib_limit(name):
+    """an enum constant of include/modet_hip_pcnet.h, read from the header the library was built from"""
+    import re
+    m = re.search(r"\b%s\s*=\s*(\d+)" % name, open(_lib.FAMILIES["pcnet"][0]).read())
+    return int(m.group(1))
+
+
+class _NffFuse(Function):
+    """pool -> gate -> apply in one node; the concatenation is never stored: the backward forms it again from the inputs"""
+
+    @staticmethod
+    def forward(ctx, t0, t1, t2, logits, W1, W2):
+        B, V, C = _nff_args("nff_fuse", t0, t1, t2, logits, W1, W2)
+        L, dev = _L(), t0.device
+        avg, mx, g = (torch.empty((B, 3 * C), dtype=torch.float32, device=dev) for _ in range(3))
+        arg = torch.empty((B, 3 * C), dtype=torch.int32, device=dev)
+        out = torch.empty(tuple(t0.shape[:-1]) + (3 * C,), dtype=torch.float32, device=dev)
+        nb = L.modet_pcnet_nff_ws_bytes(B, V, C, 0)
+        ws = _ws(nb, t0)
+        nin = 3.0 * t0.numel() + logits.numel()
+        with _Guard(t0, f"nff_pool[C{C}]", 3.0 * 3 * t0.numel(), 4.0 * nin):
+            _call(L.modet_pcnet_nff_pool, _p(t0), _p(t1), _p(t2), _p(logits), _p(avg), _p(mx), _p(arg), _p(ws), nb, B, V, C, _stream())
+        with _Guard(t0, f"nff_gate_fwd[C{C}]", 4.0 * B * 3 * C * (3 * C // 8) * 2, 4.0 * 2 * W1.numel()):
+            _call(L.modet_pcnet_nff_gate_fwd, _p(avg), _p(mx), _p(W1), _p(W2), _p(g), B, C, _stream())
+        with _Guard(t0, f"nff_apply_fwd[C{C}]", 2.0 * 3 * t0.numel(), 4.0 * (nin + out.numel())):
+            _call(L.modet_pcnet_nff_apply_fwd, _p(t0), _p(t1), _p(t2), _p(logits), _p(g), _p(out), B, V, C, _stream())
+        ctx.save_for_backward(t0, t1, t2, logits, W1, W2, avg, mx, arg, g)
+        ctx.dims = (B, V, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        t0, t1, t2, logits, W1, W2, avg, mx, arg, g = ctx.saved_tensors
+        B, V, C = ctx.dims
+        L, dev = _L(), t0.device
+        dout = dout.contiguous()
+        need = ctx.needs_input_grad
+        need_w = need[4] or need[5]
+        if not any(need):
+            return (None,) * 6
+        nin = 3.0 * t0.numel() + logits.numel()
+        dg, davg, dmx = (torch.empty((B, 3 * C), dtype=torch.float32, device=dev) for _ in range(3))
+        nb = L.modet_pcnet_nff_ws_bytes(B, V, C, 1)
+        ws = _ws(nb, t0)
+        with _Guard(t0, f"nff_apply_bwd_gate[C{C}]", 3.0 * 3 * t0.numel(), 4.0 * (nin + dout.numel())):
+            _call(L.modet_pcnet_nff_apply_bwd_gate, _p(t0), _p(t1), _p(t2), _p(logits), _p(dout), _p(dg), _p(ws), nb, B, V, C, _stream())
+        dW1 = torch.empty_like(W1) if need_w else None
+        dW2 = torch.empty_like(W2) if need_w else None
+        nb = L.modet_pcnet_nff_ws_bytes(B, V, C, 2)
+        ws = _ws(nb, t0)
+        with _Guard(t0, f"nff_gate_bwd[C{C}]", 8.0 * B * 3 * C * (3 * C // 8) * 2, 4.0 * 4 * W1.numel()):
+            _call(L.modet_pcnet_nff_gate_bwd, _p(avg), _p(mx), _p(W1), _p(W2), _p(g), _p(dg), _p(davg), _p(dmx), _p(dW1), _p(dW2),
+                  _p(ws), nb, B, C, _stream())
+        grads = [torch.empty_like(t) if n else None for t, n in zip((t0, t1, t2, logits), need[:4])]
+        if any(n for n in need[:4]):
+            nout = sum(t.numel() for t in grads if t is not None)
+            with _Guard(t0, f"nff_apply_bwd[C{C}]", 6.0 * 3 * t0.numel(), 4.0 * (nin + dout.numel() + nout)):
+                _call(L.modet_pcnet_nff_apply_bwd, _p(t0), _p(t1), _p(t2), _p(logits), _p(dout), _p(g), _p(davg), _p(dmx), _p(arg),
+                      *(_p(t) for t in grads), B, V, C, _stream())
+        return (*grads, dW1 if need[4] else None, dW2 if need[5] else None)
+
+
+def nff_fuse(t0, t1, t2, logits, W1, W2):
+    """The tail of NFFBlock.forward ("Baseline methods/PCnet/models.py":316-322, 285-292): w = softmax(logits) over its 3 entries,
+    cat = [t0 w0, t1 w1, t2 w2] along the channels, g = sigmoid(fc(avgpool(cat)) + fc(maxpool(cat))) with fc = W2 relu(W1 .),
+    returns cat * g, (B,D,H,W,3C).  t_k (B,D,H,W,C), logits (B,D,H,W,3), W1 (3C // 8, 3C), W2 (3C, 3C // 8)."""
+    return _NffFuse.apply(t0, t1, t2, logits, W1, W2)
+
+
+def residual_add(a, b):
+    """a + b elementwise in one kernel (ResBlock's ``self.block(x) + x``); autograd's own accumulation carries the gradient to
+    both addends"""
+    return _ResidualAdd.apply(a, b)
+
+
+class _ResidualAdd(Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        _chk(a, b)
+        _same_shape("residual_add", "b", b, tuple(a.shape), "a")
+        if a.numel() < 1:
+            raise RuntimeError(f"residual_add: a {tuple(a.shape)} is empty")
+        s = torch.empty_like(a)
+        with _Guard(a, "residual_add", float(a.numel()), 12.0 * a.numel()):
+            _call(_L().modet_pcnet_add, _p(a), _p(b), _p(s), a.numel(), _stream())
+        return s
+
+    @staticmethod
+    def backward(ctx, ds):
+        return ds, ds
+
+
 class _ToCL(Function):
     @staticmethod
     def forward(ctx, x):

@@ -7,6 +7,7 @@
     python -m smilecode_amd.train --model im2grid ...      # the Im2Grid baseline ("Baseline methods/Im2Grid/train.py"), its directory name
     python -m smilecode_amd.train --model rdn --channels 16 --levels 1,1,1,1 [--diff] ...   # the RDN baseline ("Baseline methods/RDN/train.py")
     python -m smilecode_amd.train --model rcn --channels 8 --cascades 10 --img-size 192,192,192 ...   # the RCN baseline ("Baseline methods/RCN/train.py")
+    python -m smilecode_amd.train --model pcnet --channels 16 ...   # the PCNet baseline ("Baseline methods/PCnet/train.py")
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ import torch
 from . import data, utils
 from .engine import Trainer, poly_lr
 from .losses import REG_TERMS, SIM_TERMS
-from .models import RCN, RDN, Im2grid, ModeT
+from .models import RCN, RDN, Im2grid, ModeT, PCNet
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
 
@@ -72,7 +73,7 @@ def latest_checkpoint(model_dir):
     return os.path.join(model_dir, files[-1])
 
 
-MODELS = ("modet", "im2grid", "rdn", "rcn")       # --model of train.py and infer.py
+MODELS = ("modet", "im2grid", "rdn", "rcn", "pcnet")       # --model of train.py and infer.py
 
 
 def make_parser():
@@ -112,9 +113,11 @@ def make_parser():
                          "coordinate translator per level; fp32, no --diff, no --overlap-allreduce), or the RDN baseline (stride-2 "
                          "encoder, one Estimator per level; fp32, one stage, --diff = its RDN_diff form, no --overlap-allreduce), or the RCN "
                          "baseline (--cascades VTNs on stride-2 and transposed convolutions, flow_multiplier 2; fp32, --channels 4 or 8, every "
-                         "size a multiple of 64, no --diff, no --overlap-allreduce; the regulariser applies to every cascade's subflow)")
+                         "size a multiple of 64, no --diff, no --overlap-allreduce; the regulariser applies to every cascade's subflow), or the "
+                         "PCNet baseline (two residual encoders, DFI and NFF blocks on fused kernels; fp32, --channels 4, 8, 12 or 16, every "
+                         "size a multiple of 8, no --diff: its fields are always integrated; no --overlap-allreduce)")
     ap.add_argument("--channels", type=int, default=16,
-                    help="--model rdn / rcn: channels of the first encoder layer (the references' default; rcn runs 4 or 8)")
+                    help="--model rdn / rcn / pcnet: channels of the first encoder layer (the references' default; rcn runs 4 or 8)")
     ap.add_argument("--cascades", type=int, default=10, help="--model rcn: number of cascaded VTNs (the reference's n_cascade)")
     ap.add_argument("--levels", default="1,1,1,1",
                     help="--model rdn: Estimator passes per level a,b,c,d, finest level first (the reference's level_recursion)")
@@ -149,6 +152,11 @@ def check_model_args(ap, args):
             ap.error("--overlap-allreduce is ModeT's: the three-stage bucket cut follows ModeT's layers")
         if getattr(args, "cascades", 10) < 1:
             ap.error("--cascades takes a positive number of VTNs, got {!r}".format(args.cascades))
+    if args.model == "pcnet":
+        if args.diff:
+            ap.error("--diff is ModeT's and RDN's: the PCNet baseline integrates every field it composes as it is")
+        if getattr(args, "overlap_allreduce", False):
+            ap.error("--overlap-allreduce is ModeT's: the three-stage bucket cut follows ModeT's layers")
     return args
 
 
@@ -158,6 +166,8 @@ def make_model(args, img_size, training=False):
         return Im2grid(img_size)
     if args.model == "rcn":                                     # "Baseline methods/RCN/train.py":69, infer.py:59
         return RCN(img_size, flow_multiplier=2, channels=args.channels, n_cascade=args.cascades, return_subflows=training)
+    if args.model == "pcnet":                                   # "Baseline methods/PCnet/train.py":65
+        return PCNet(img_size, channels=args.channels)
     if args.model == "rdn":
         return RDN(img_size, channels=args.channels, level_recursion=rdn_levels(args), diff=args.diff, int_steps=args.int_steps)
     return ModeT(img_size, head_dim=6, num_heads=[8, 4, 2, 1, 1], scale=1, diff=args.diff, int_steps=args.int_steps)
@@ -171,6 +181,8 @@ def save_dir_name(args, num_heads, head_dim, weights):
         return "Im2Grid_{}_{}_reg_{}{}_lr_{}_54r/".format(args.sim, weights[0], reg, weights[1], args.lr)
     if getattr(args, "model", "modet") == "rcn":            # "Baseline methods/RCN/train.py":50
         return "RCN_{}_{}_reg_{}{}_lr_{}_54r/".format(args.sim, weights[0], reg, weights[1], args.lr)
+    if getattr(args, "model", "modet") == "pcnet":          # "Baseline methods/PCnet/train.py":49
+        return "PCnet_{}_{}_reg_{}{}_lr_{}_54r/".format(args.sim, weights[0], reg, weights[1], args.lr)
     diff = "_diff{}".format(args.int_steps) if getattr(args, "diff", False) else ""
     if getattr(args, "model", "modet") == "rdn":            # "Baseline methods/RDN/train.py":51 (its "diffusion" is the regulariser's weight)
         return "RDN({}, {}{}{}{})_{}_{}_diffusion_{}{}_lr_{}{}/".format(1, *rdn_levels(args), args.sim, weights[0], reg, weights[1], args.lr, diff)
