@@ -215,6 +215,19 @@ FAMILIES = {
         "modet_pcnet_nff_apply_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I64, I, P]),
         "modet_pcnet_add": (I, [P, P, P, I64, P]),
     }),
+    "prpp": (_header("modet_hip_prpp.h"), {
+        "modet_prpp_upcat_fwd": (I, [P, P, P, I, I, I, I, I, I, P]),
+        "modet_prpp_upcat_bwd": (I, [P, P, P, I, I, I, I, I, I, P]),
+        "modet_prpp_relu_fwd": (I, [P, P, I64, P]),
+        "modet_prpp_relu_add_fwd": (I, [P, P, P, I64, P]),
+        "modet_prpp_relu_bwd": (I, [P, P, P, I64, P]),
+        "modet_prpp_stack_ws_bytes": (SZ, [I, I, I, I, I]),
+        "modet_prpp_stack_fwd": (I, [P, P, P, P, SZ, I, I, I, I, I, P]),
+        "modet_prpp_stack_bwd": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, P]),
+        "modet_prpp_compose_ws_bytes": (SZ, [I, I, I, I]),
+        "modet_prpp_compose_fwd": (I, [P, P, P, I, I, I, I, I, I, I, P]),
+        "modet_prpp_compose_bwd": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, I, I, P]),
+    }),
 }
 # The names a family's entry had before the registry.  Nothing in this tree uses them; they stay because the previous revision's
 # test files, which every change is also run against, reach the library through them (about 95 test ids).  Views of FAMILIES:

@@ -42,7 +42,10 @@ int modet_hip_version(void) { return 447;
               (include/modet_hip_deconv.h): the 4x4x4 transposed convolution with stride 2 and padding 1 and a fused
               LeakyReLU(slope) of the RCN / VTN and PCNet decoders, any channel count up to 1024, on LDS-staged 3-D tiles
      0.4.4.8: + the twelve modet_pcnet_* entry points (include/modet_hip_pcnet.h): trilinear upsampling by 2 / 4 / 8 into a slice of
-              a wider row, DFI's gated sum, the NFF tail (pool, gate, apply and their backward passes) and the residual sum */ }
+              a wider row, DFI's gated sum, the NFF tail (pool, gate, apply and their backward passes) and the residual sum
+     0.4.4.9: + the twelve modet_prpp_* entry points (include/modet_hip_prpp.h): nearest upsampling by 2 + concatenation, ReLU and
+              x + relu(t), the PR++ block's stack [mov | correlation | fix] as one row (corr3d's kernels, now in corr3d_internal.h)
+              and the composition of a flow on a coarser grid with a field on the finer one (fixed-point deterministic scatter) */ }
 
 const char* modet_hip_strerror(int code) {
   switch (code) {

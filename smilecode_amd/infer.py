@@ -8,6 +8,7 @@ fraction of voxels with non-positive Jacobian determinant; with --surface also H
     python -m smilecode_amd.infer --model rdn --channels 16 --levels 1,1,1,1 --model-dir experiments/<run>/   # an RDN checkpoint
     python -m smilecode_amd.infer --model rcn --channels 8 --cascades 10 --img-size 192,192,192 --model-dir experiments/<run>/   # an RCN checkpoint
     python -m smilecode_amd.infer --model pcnet --channels 16 --model-dir experiments/<run>/   # a PCNet checkpoint
+    python -m smilecode_amd.infer --model prpp --channels 8 --model-dir experiments/<run>/     # a PR++ checkpoint
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ import os
 import torch
 
 from . import data, utils
-from .train import MODELS, _natkey, check_model_args, make_model
+from .train import MODELS, _Given, _natkey, check_model_args, make_model
 
 
 def make_parser():
@@ -33,7 +34,8 @@ def make_parser():
     ap.add_argument("--surface", action="store_true",
                     help="also report HD95 and ASSD (voxels) of the warped and the raw labels, computed on the GPU")
     ap.add_argument("--model", choices=MODELS, default="modet", help="the network the checkpoint was trained with (train --model)")
-    ap.add_argument("--channels", type=int, default=16, help="--model rdn / rcn / pcnet: channels of the first encoder layer, as trained")
+    ap.add_argument("--channels", type=int, default=16, action=_Given,
+                    help="--model rdn / rcn / pcnet / prpp: channels of the first encoder layer, as trained (prpp: 8 unless given)")
     ap.add_argument("--cascades", type=int, default=10, help="--model rcn: number of cascaded VTNs, as trained")
     ap.add_argument("--levels", default="1,1,1,1", help="--model rdn: Estimator passes per level a,b,c,d, finest level first, as trained")
     return ap

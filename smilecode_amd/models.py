@@ -1438,6 +1438,220 @@ class PCNet(nn.Module):
             return ops.warp_tee(mov_cl, flow)       # (the flow's other consumer: the caller, Grad3d in training)
 
 
+class ConvBlockReLU(nn.Module):
+    """PR++'s ConvBlock ("Baseline methods/PR++/models.py":113-127): nn.Conv3d(cin, cout, 3, stride, 1) + ReLU; channels-last.
+    Stride 2 is one fused kernel (ops.conv3d_s2 with slope 0); stride 1 is the plain stride-1 entry point, which makes no
+    assumption about its input's range (the first layer sees the raw image, and nothing normalises the later ones), then ops.relu."""
+
+    def __init__(self, in_channels, out_channels, stride=1):
+        super().__init__()
+        if stride not in (1, 2):
+            raise RuntimeError(f"ConvBlock: stride = {stride!r}: the convolution kernels have strides 1 and 2")
+        self.main = _Conv3dParams(in_channels, out_channels)
+        self.stride = stride
+
+    def forward(self, x):
+        if self.stride == 2:
+            return ops.conv3d_s2(x, self.main.weight, self.main.bias, 0.0)
+        return ops.relu(ops.conv3d(x, self.main.weight, self.main.bias, False))
+
+
+class EncoderReLU(nn.Module):
+    """PR++'s Encoder (":132-148): c, 2c, 2c, 4c, 4c channels at 1, 1/2, 1/4, 1/8, 1/16"""
+
+    def __init__(self, in_channel=1, first_channel=8):
+        super().__init__()
+        c = first_channel
+        self.block1 = ConvBlockReLU(in_channel, c)
+        self.block2 = ConvBlockReLU(c, c * 2, stride=2)
+        self.block3 = ConvBlockReLU(c * 2, c * 2, stride=2)
+        self.block4 = ConvBlockReLU(c * 2, c * 4, stride=2)
+        self.block5 = ConvBlockReLU(c * 4, c * 4, stride=2)
+
+    def forward(self, x):
+        outs = [self.block1(x)]
+        for blk in (self.block2, self.block3, self.block4, self.block5):
+            outs.append(blk(outs[-1]))
+        return outs
+
+
+class DecoderBlock(nn.Module):
+    """PR++'s DecoderBlock (":150-160): nearest upsampling by 2, concatenation with the skip (one kernel,
+    ops.upsample_nearest_cat), ConvBlock.  ``Upsample`` is the reference's (parameter-free) attribute."""
+
+    def __init__(self, deconv_channel, skip_channel, out_channel):
+        super().__init__()
+        self.Upsample = nn.Identity()
+        self.Conv = ConvBlockReLU(deconv_channel + skip_channel, out_channel)
+
+    def forward(self, x, skip):
+        return self.Conv(ops.upsample_nearest_cat(x, skip))
+
+
+class BackBone(nn.Module):
+    """PR++'s BackBone (":162-191) on ONE batch: the reference runs encoder and decoder once per image with shared weights and no
+    layer mixes samples, so [moving; fixed] goes through as a batch of 2 B -- which also makes every weight the operand of exactly
+    one convolution per pass.  Returns the five decoder outputs, (4c, 1/8), (4c, 1/4), (2c, 1/2), (2c, 1), (c, 1)."""
+
+    def __init__(self, in_channel=1, first_channel=8):
+        super().__init__()
+        c = first_channel
+        self.encoder = EncoderReLU(in_channel, c)
+        self.decoder1 = DecoderBlock(c * 4, c * 4, c * 4)
+        self.decoder2 = DecoderBlock(c * 4, c * 2, c * 4)
+        self.decoder3 = DecoderBlock(c * 4, c * 2, c * 2)
+        self.decoder4 = DecoderBlock(c * 2, c, c * 2)
+        self.decoder5 = ConvBlockReLU(2 * c, c)
+
+    def forward(self, x):
+        f5, f4, f3, f2, f1 = self.encoder(x)
+        o1 = self.decoder1(f1, f2)
+        o2 = self.decoder2(o1, f3)
+        o3 = self.decoder3(o2, f4)
+        o4 = self.decoder4(o3, f5)
+        return [o1, o2, o3, o4, self.decoder5(o4)]
+
+
+class PRplusplusBlock(nn.Module):
+    """PR++'s block (":244-282): [x2 upsampling of 2 flow,] warp of x, the stack [x | Correlation3D(x, y) | y] (one kernel,
+    ops.corr_stack), conv1 = two convolutions + ReLU, conv2 likewise, the 3-channel convolution of x + res (ops.relu_add).
+    ``conv1`` / ``conv2`` keep nn.Sequential's indices 0, 1 (2 is the ReLU); ``stn.grid`` as ModeT handles it.  The flow
+    convolution starts as Normal(0, 1e-5) with zero bias."""
+
+    def __init__(self, size, in_channel, in_flow=True, scale=True, kernel_size=3, d=3, sw=1, sf=2, legacy_grid_buffers=False):
+        super().__init__()
+        if (kernel_size, d, sw, sf) != (3, 3, 1, 2):
+            raise RuntimeError(f"PRplusplusBlock: kernel_size, d, sw, sf = {(kernel_size, d, sw, sf)}: the correlation kernels are built for (3, 3, 1, 2)")
+        self.scale, self.in_flow = bool(scale), bool(in_flow)
+        if in_flow:
+            self.stn = SpatialTransformer(size, legacy_grid_buffers=legacy_grid_buffers)
+        C, R = in_channel, in_channel * 2 + ops.PRPP_CORR
+        self.conv1 = nn.ModuleList([_Conv3dParams(R, R), _Conv3dParams(R, C), nn.Identity()])
+        self.conv2 = nn.ModuleList([_Conv3dParams(C, C), _Conv3dParams(C, C), nn.Identity()])
+        self.flow = _Conv3dParams(C, 3)
+        with torch.no_grad():
+            self.flow.weight.normal_(0.0, 1e-5)
+            self.flow.bias.zero_()
+
+    def forward(self, x, y, flow=None):
+        if self.in_flow:
+            if self.scale:
+                flow = ops.upsample2(flow, 2.0)
+            x = self.stn.forward_cl(x, flow)
+        h = ops.corr_stack(x, y)
+        h = ops.conv3d(h, self.conv1[0].weight, self.conv1[0].bias, False)
+        h = ops.relu(ops.conv3d(h, self.conv1[1].weight, self.conv1[1].bias, False))
+        res = ops.conv3d(h, self.conv2[0].weight, self.conv2[0].bias, False)
+        res = ops.conv3d(res, self.conv2[1].weight, self.conv2[1].bias, False)
+        return ops.conv3d(ops.relu_add(h, res), self.flow.weight, self.flow.bias, False)
+
+
+PRPP_MAX_STRIDE1_WIDTH = 256        # the widest stride-1 convolution is a block's 8c + 27 -> 8c + 27 (csrc/conv3d.hip: up to 256 channels)
+
+
+def prpp_unsupported_config(in_channel=1, first_channel=8, act_dtype=torch.float32, diff=False, overlap_allreduce=False):
+    """None if every kernel on PR++'s path accepts the configuration, else a message naming the argument"""
+    if act_dtype != torch.float32:
+        return f"act_dtype = {act_dtype}: the stride-2, stack and composition kernels are fp32 only (bf16 storage is ModeT's)"
+    if diff:
+        return "diff = True: the reference has no diffeomorphic PR++; flow integration (VecInt) is ModeT's, RDN's and PCNet's"
+    if overlap_allreduce:
+        return "overlap_allreduce = True: the overlapped all-reduce cuts the backward at ModeT's three bucket boundaries, which PR++ does not have"
+    if isinstance(in_channel, bool) or int(in_channel) != in_channel or in_channel < 1:
+        return f"in_channel = {in_channel}: a positive integer"
+    c = first_channel
+    if isinstance(c, bool) or int(c) != c or c < 4 or c % 4 != 0:
+        return (f"first_channel = {first_channel}: a positive multiple of 4 (the stride-2 layers, the decoder's 16-byte rows and the "
+                f"stack kernels take channel counts that are multiples of 4)")
+    if 8 * c + ops.PRPP_CORR > PRPP_MAX_STRIDE1_WIDTH:
+        return (f"first_channel = {first_channel}: the coarsest blocks convolve {8 * c + ops.PRPP_CORR} -> {8 * c + ops.PRPP_CORR} channels; the "
+                f"stride-1 kernels take up to {PRPP_MAX_STRIDE1_WIDTH}, so first_channel is a multiple of 4 from 4 to "
+                f"{(PRPP_MAX_STRIDE1_WIDTH - ops.PRPP_CORR) // 32 * 4}")
+    L = ops._L()
+    for cin, cout in [(c, 2 * c), (2 * c, 2 * c), (2 * c, 4 * c), (4 * c, 4 * c)]:
+        if L.modet_convs2_ws_bytes(1, 16, 16, 16, cin, cout, 0) == 0:
+            return f"first_channel = {first_channel}: the encoder's stride-2 layer {cin} -> {cout} is refused by the convs2 kernels"
+    if L.modet_prpp_stack_ws_bytes(1, 2, 2, 2, 4 * c) == 0:
+        return f"first_channel = {first_channel}: the stack kernels refuse {4 * c} channels per map"
+    return None
+
+
+class PRNetplusplus(nn.Module):
+    """The PR++ baseline ("Baseline methods/PR++/models.py":318-352, the model its train.py trains): a five-level ReLU U-Net shared
+    by both images, five PRplusplusBlocks from the 1/8 grid to full resolution, each predicting a field w from the stack of the
+    warped moving features, their 27-displacement correlation with the fixed ones and the fixed features, and the running
+    ``flow = transformers[k](flow, w) + w``.  For blocks 2-4 ``flow`` lives on the grid HALF as fine as w's and is sampled there
+    as the reference's SpatialTransformer does (ops.compose_cross: not upsample-then-warp, and no factor 2); block 5 composes on
+    one grid.  Same constructor arguments, attribute names and state-dict keys as the reference (``net.encoder.blockN.main.*``,
+    ``net.decoderN.Conv.main.*``, ``net.decoder5.main.*``, ``prblockN.conv{1,2}.{0,1}.*``, ``prblockN.flow.*``; ``prblockN.stn.grid``
+    and ``transformers.N.grid`` as ModeT handles them, ``legacy_grid_buffers``).  ``forward(moving, fixed)`` returns
+    ``(y_moved, flow)``.  fp32 only."""
+
+    stage_buckets = False       # engine.Trainer: the three-stage bucket cut of the overlapped all-reduce is ModeT's
+
+    def __init__(self, size=(80, 96, 80), in_channel=1, first_channel=8, legacy_grid_buffers=False, act_dtype=torch.float32,
+                 diff=False, overlap_allreduce=False):
+        super().__init__()
+        why = prpp_unsupported_config(in_channel, first_channel, act_dtype, diff, overlap_allreduce)
+        if why is not None:
+            raise RuntimeError("PRNetplusplus: " + why)
+        why = self.unsupported_shape(size)
+        if why is not None:
+            raise RuntimeError("PRNetplusplus: size: " + why)
+        self.inshape = tuple(int(s) for s in size)
+        self.channels = first_channel
+        self.act_dtype = act_dtype
+        c, lg = first_channel, legacy_grid_buffers
+        shape = lambda k: [s // k for s in self.inshape]          # noqa: E731
+        self.net = BackBone(in_channel, c)
+        self.prblock1 = PRplusplusBlock(None, 4 * c, in_flow=False, scale=False)
+        self.prblock2 = PRplusplusBlock(shape(4), 4 * c, legacy_grid_buffers=lg)
+        self.prblock3 = PRplusplusBlock(shape(2), 2 * c, legacy_grid_buffers=lg)
+        self.prblock4 = PRplusplusBlock(shape(1), 2 * c, legacy_grid_buffers=lg)
+        self.prblock5 = PRplusplusBlock(shape(1), c, scale=False, legacy_grid_buffers=lg)
+        self.transformers = nn.ModuleList([SpatialTransformer(shape(2 ** i), legacy_grid_buffers=lg) for i in range(3)])
+        self.up = nn.Identity()     # the reference's ResizeTransform: an attribute its forward never calls
+
+    @staticmethod
+    def unsupported_shape(shape):
+        """None, or why a (D,H,W) volume cannot go through the four stride-2 levels and back"""
+        shape = tuple(shape)
+        if len(shape) != 3:
+            return f"(D, H, W) expected, got {shape}"
+        if any(int(v) % 16 != 0 or int(v) < 16 for v in shape):
+            return (f"every spatial dimension must be a positive multiple of 16 (four stride-2 layers, and each nearest x2 upsampling "
+                    f"of the decoder must meet its skip exactly), got {shape}")
+        return None
+
+    def forward(self, moving, fixed):
+        """(y_moved (B,1,D,H,W), flow (B,3,D,H,W))"""
+        return tuple(ops.to_ncdhw(t) for t in self.forward_cl(moving, fixed))
+
+    def forward_cl(self, moving, fixed):
+        """``forward`` with the results channels-last, as the kernels wrote them: y_moved (B,D,H,W,1), flow (B,D,H,W,3)"""
+        if moving.shape != fixed.shape or moving.dim() != 5:
+            raise RuntimeError("PRNetplusplus.forward expects two (B,C,D,H,W) volumes of the same shape")
+        why = self.unsupported_shape(moving.shape[2:])
+        if why is not None:
+            raise RuntimeError("PRNetplusplus.forward: " + why)
+        B = moving.shape[0]
+        mov_cl = ops.to_channels_last(moving.contiguous())
+        fix_cl = ops.to_channels_last(fixed.contiguous())
+        with ops.trace_range("backbone"):
+            X, Y = zip(*(_SplitBatch.apply(f, B) for f in self.net(ops.cat_batch(mov_cl, fix_cl))))
+        with ops.trace_range("level1"):
+            flow = self.prblock1(X[0], Y[0])
+        # the running flow has two consumers per level (the next block's warp and the composition): autograd adds the two gradients
+        for k, blk in ((1, self.prblock2), (2, self.prblock3), (3, self.prblock4)):
+            with ops.trace_range("level%d" % (k + 1)):
+                flow = ops.compose_cross(flow, blk(X[k], Y[k], flow))
+        with ops.trace_range("level5"):
+            w = self.prblock5(X[4], Y[4], flow)
+            flow = self.transformers[0].forward_cl(flow, w, add_flow=True)
+        with ops.trace_range("output"):
+            return ops.warp_tee(mov_cl, flow)       # (the flow's other consumer: the caller, Grad3d in training)
+
+
 def load_numpy_weights(model: nn.Module, weights) -> None:
     """copy a name -> ndarray dict (smilecode_amd.synth.make_weights) into the model's parameters"""
     params = dict(model.named_parameters())

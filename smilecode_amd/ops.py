@@ -2085,6 +2085,208 @@ class _ResidualAdd(Function):
         return ds, ds
 
 
+# ------------------------------------------------------------------------------------------------ the PR++ family
+PRPP_CORR = 27                   # MODET_PRPP_CORR of include/modet_hip_prpp.h: the correlation channels of a stack row
+
+
+def _prpp_limit(name):
+    """an enum constant of include/modet_hip_prpp.h, read from the header the library was built from"""
+    import re
+    return int(re.search(r"\b%s\s*=\s*(\d+)" % name, open(_lib.FAMILIES["prpp"][0]).read()).group(1))
+
+
+class _UpsampleNearestCat(Function):
+    @staticmethod
+    def forward(ctx, x, skip):
+        op = "upsample_nearest_cat"
+        _chk(x, skip)
+        _rank5(op, "x", x)
+        _rank5(op, "skip", skip)
+        B, d, h, w, C1 = x.shape
+        C2 = skip.shape[-1]
+        if B < 1 or min(d, h, w, C1, C2) < 1:
+            raise RuntimeError(f"{op}: x {tuple(x.shape)} or skip {tuple(skip.shape)} is empty")
+        _same_shape(op, "skip", skip, (B, 2 * d, 2 * h, 2 * w, C2), f"x {tuple(x.shape)} upsampled by 2")
+        out = torch.empty((B, 2 * d, 2 * h, 2 * w, C1 + C2), dtype=torch.float32, device=x.device)
+        with _Guard(x, f"upcat_fwd[{C1}+{C2}]", 0.0, 4.0 * (x.numel() + skip.numel() + out.numel())):
+            _call(_L().modet_prpp_upcat_fwd, _p(x), _p(skip), _p(out), B, d, h, w, C1, C2, _stream())
+        ctx.dims = (B, d, h, w, C1, C2)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, d, h, w, C1, C2 = ctx.dims
+        dout = dout.contiguous()
+        dx = torch.empty((B, d, h, w, C1), dtype=torch.float32, device=dout.device) if ctx.needs_input_grad[0] else None
+        ds = torch.empty((B, 2 * d, 2 * h, 2 * w, C2), dtype=torch.float32, device=dout.device) if ctx.needs_input_grad[1] else None
+        if dx is not None or ds is not None:
+            nout = sum(t.numel() for t in (dx, ds) if t is not None)
+            with _Guard(dout, f"upcat_bwd[{C1}+{C2}]", 7.0 * (0 if dx is None else dx.numel()), 4.0 * (dout.numel() + nout)):
+                _call(_L().modet_prpp_upcat_bwd, _p(dout), _p(dx), _p(ds), B, d, h, w, C1, C2, _stream())
+        return dx, ds
+
+
+def upsample_nearest_cat(x, skip):
+    """torch.cat([nn.Upsample(scale_factor=2)(x), skip], channels) of channels-last x (B,d,h,w,C1) and skip (B,2d,2h,2w,C2) in one
+    pass: DecoderBlock.forward before its convolution ("Baseline methods/PR++/models.py":150-160); the backward gathers d_x"""
+    return _UpsampleNearestCat.apply(x, skip)
+
+
+class _Relu(Function):
+    @staticmethod
+    def forward(ctx, t):
+        _chk(t)
+        if t.numel() < 1:
+            raise RuntimeError(f"relu: t {tuple(t.shape)} is empty")
+        y = torch.empty_like(t)
+        with _Guard(t, "relu_fwd", float(t.numel()), 8.0 * t.numel()):
+            _call(_L().modet_prpp_relu_fwd, _p(t), _p(y), t.numel(), _stream())
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dt = torch.empty_like(dy)
+        with _Guard(dy, "relu_bwd", float(dy.numel()), 12.0 * dy.numel()):
+            _call(_L().modet_prpp_relu_bwd, _p(dy), _p(y), _p(dt), dy.numel(), _stream())
+        return dt
+
+
+def relu(t):
+    """max(t, 0) (nn.ReLU of the PR++ ConvBlock and blocks); the gradient at 0 is 0"""
+    return _Relu.apply(t)
+
+
+class _ReluAdd(Function):
+    @staticmethod
+    def forward(ctx, x, t):
+        _chk(x, t)
+        _same_shape("relu_add", "t", t, tuple(x.shape), "x")
+        if x.numel() < 1:
+            raise RuntimeError(f"relu_add: x {tuple(x.shape)} is empty")
+        out = torch.empty_like(x)
+        with _Guard(x, "relu_add_fwd", 2.0 * x.numel(), 12.0 * x.numel()):
+            _call(_L().modet_prpp_relu_add_fwd, _p(x), _p(t), _p(out), x.numel(), _stream())
+        ctx.save_for_backward(t)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (t,) = ctx.saved_tensors
+        dt = None
+        if ctx.needs_input_grad[1]:
+            dout = dout.contiguous()
+            dt = torch.empty_like(dout)
+            with _Guard(dout, "relu_bwd", float(dout.numel()), 12.0 * dout.numel()):
+                _call(_L().modet_prpp_relu_bwd, _p(dout), _p(t), _p(dt), dout.numel(), _stream())
+        return dout, dt          # d_x is d_out itself: autograd accumulates it (as residual_add)
+
+
+def relu_add(x, t):
+    """x + max(t, 0) in one pass: ``x + res`` of PRplusplusBlock.forward with conv2's trailing ReLU ("Baseline methods/PR++/
+    models.py":261-281)"""
+    return _ReluAdd.apply(x, t)
+
+
+def _stack_args(op, mov, fix):
+    _chk(mov, fix)
+    _rank5(op, "mov", mov)
+    _same_shape(op, "fix", fix, tuple(mov.shape), "mov")
+    B, D, H, W, C = mov.shape
+    if B < 1 or min(D, H, W) < 1:
+        raise RuntimeError(f"{op}: mov {tuple(mov.shape)} is empty")
+    nb = _L().modet_prpp_stack_ws_bytes(B, D, H, W, C)
+    if nb == 0:
+        raise RuntimeError(f"{op}: mov {tuple(mov.shape)}: the kernels take a channel count that is a multiple of 4 from 4 to "
+                           f"{_prpp_limit('MODET_PRPP_MAX_C')} and fewer than 2^31 elements on the grid extended by one voxel")
+    return B, D, H, W, C, nb
+
+
+class _CorrStack(Function):
+    @staticmethod
+    def forward(ctx, mov, fix):
+        B, D, H, W, C, nb = _stack_args("corr_stack", mov, fix)
+        out = torch.empty((B, D, H, W, 2 * C + PRPP_CORR), dtype=torch.float32, device=mov.device)
+        ws = _ws(nb, mov)
+        n = float(B) * D * H * W
+        with _Guard(mov, f"corr_stack_fwd[C{C}]", n * C * (54.0 + 54.0), 4.0 * n * (4 * C + 27)):
+            _call(_L().modet_prpp_stack_fwd, _p(mov), _p(fix), _p(out), _p(ws), nb, B, D, H, W, C, _stream())
+        ctx.save_for_backward(mov, fix)
+        ctx.nb = nb
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        mov, fix = ctx.saved_tensors
+        B, D, H, W, C = mov.shape
+        dout = dout.contiguous()
+        dmov = torch.empty_like(mov) if ctx.needs_input_grad[0] else None
+        dfix = torch.empty_like(fix) if ctx.needs_input_grad[1] else None
+        if dmov is not None or dfix is not None:
+            ws = _ws(ctx.nb, mov)
+            n = float(B) * D * H * W
+            with _Guard(mov, f"corr_stack_bwd[C{C}]", n * C * 4 * 54.0, 4.0 * n * (6 * C + 27)):
+                _call(_L().modet_prpp_stack_bwd, _p(mov), _p(fix), _p(dout), _p(dmov), _p(dfix), _p(ws), ctx.nb, B, D, H, W, C, _stream())
+        return dmov, dfix
+
+
+def corr_stack(mov, fix):
+    """torch.cat([mov, Correlation3D(mov, fix), fix], channels) of channels-last features (B,D,H,W,C) -> (B,D,H,W,2C+27): the stack
+    of PRplusplusBlock.forward ("Baseline methods/PR++/models.py":276-278) in one row, the correlation by correlation3d's kernels"""
+    return _CorrStack.apply(mov, fix)
+
+
+def _compose_args(op, src, w):
+    _chk(src, w)
+    _rank5(op, "src", src)
+    _rank5(op, "w", w)
+    if src.shape[-1] != 3 or w.shape[-1] != 3 or src.shape[0] != w.shape[0]:
+        raise RuntimeError(f"{op}: src {tuple(src.shape)} and w {tuple(w.shape)} must be 3-channel fields of one batch")
+    if src.shape[0] < 1 or min(src.shape[1:4]) < 1 or min(w.shape[1:4]) < 2:
+        raise RuntimeError(f"{op}: src {tuple(src.shape)} needs a voxel and w {tuple(w.shape)} two voxels along every axis "
+                           "(align_corners=True has no scale for an axis of 1)")
+    return (src.shape[0],) + tuple(src.shape[1:4]) + tuple(w.shape[1:4])
+
+
+class _ComposeCross(Function):
+    @staticmethod
+    def forward(ctx, src, w):
+        dims = _compose_args("compose_cross", src, w)
+        out = torch.empty_like(w)
+        n = float(w.numel() // 3)
+        with _Guard(w, "compose_cross_fwd", n * 102.0, 4.0 * (src.numel() + 2 * w.numel())):
+            _call(_L().modet_prpp_compose_fwd, _p(src), _p(w), _p(out), *dims, _stream())
+        ctx.save_for_backward(src, w)
+        ctx.dims = dims
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        src, w = ctx.saved_tensors
+        dout = dout.contiguous()
+        dsrc = torch.empty_like(src) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
+        if dsrc is None and dw is None:
+            return None, None
+        L = _L()
+        nb = L.modet_prpp_compose_ws_bytes(*ctx.dims[:4]) if dsrc is not None else 0
+        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=w.device) if nb else None
+        n = float(w.numel() // 3)
+        with _Guard(w, "compose_cross_bwd", n * 200.0, 4.0 * (3 * src.numel() + 3 * w.numel()) + 2.0 * nb):
+            _call(L.modet_prpp_compose_bwd, _p(src), _p(w), _p(dout), _p(dsrc), _p(dw), _p(ws), nb, *ctx.dims, _stream())
+        return dsrc, dw
+
+
+def compose_cross(src, w):
+    """SpatialTransformer(w's grid)(src, w) + w for a field ``src`` (B,Dc,Hc,Wc,3) on ANOTHER grid than ``w`` (B,Df,Hf,Wf,3), as
+    PRNetplusplus.forward composes the coarse flow with a block's field ("Baseline methods/PR++/models.py":338-345): the sample
+    point is (p + w) (Sc - 1) / (Sf - 1) in src's coordinates, corners outside contribute zero, src is not rescaled.  This is not
+    upsample-then-warp.  The backward's d_src is a deterministic fixed-point scatter in every mode."""
+    return _ComposeCross.apply(src, w)
+
+
 class _ToCL(Function):
     @staticmethod
     def forward(ctx, x):

@@ -8,6 +8,7 @@
     python -m smilecode_amd.train --model rdn --channels 16 --levels 1,1,1,1 [--diff] ...   # the RDN baseline ("Baseline methods/RDN/train.py")
     python -m smilecode_amd.train --model rcn --channels 8 --cascades 10 --img-size 192,192,192 ...   # the RCN baseline ("Baseline methods/RCN/train.py")
     python -m smilecode_amd.train --model pcnet --channels 16 ...   # the PCNet baseline ("Baseline methods/PCnet/train.py")
+    python -m smilecode_amd.train --model prpp --channels 8 ...     # the PR++ baseline ("Baseline methods/PR++/train.py")
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ import torch
 from . import data, utils
 from .engine import Trainer, poly_lr
 from .losses import REG_TERMS, SIM_TERMS
-from .models import RCN, RDN, Im2grid, ModeT, PCNet
+from .models import RCN, RDN, Im2grid, ModeT, PCNet, PRNetplusplus
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
 
@@ -73,7 +74,18 @@ def latest_checkpoint(model_dir):
     return os.path.join(model_dir, files[-1])
 
 
-MODELS = ("modet", "im2grid", "rdn", "rcn", "pcnet")       # --model of train.py and infer.py
+MODELS = ("modet", "im2grid", "rdn", "rcn", "pcnet", "prpp")       # --model of train.py and infer.py
+
+
+class _Given(argparse.Action):
+    """store the value and remember that the option was given (--model prpp has a default of its own for --channels)"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "_given", True)
+
+
+PRPP_CHANNELS = 8           # PRNetplusplus's first_channel default ("Baseline methods/PR++/models.py":319)
 
 
 def make_parser():
@@ -115,9 +127,12 @@ def make_parser():
                          "baseline (--cascades VTNs on stride-2 and transposed convolutions, flow_multiplier 2; fp32, --channels 4 or 8, every "
                          "size a multiple of 64, no --diff, no --overlap-allreduce; the regulariser applies to every cascade's subflow), or the "
                          "PCNet baseline (two residual encoders, DFI and NFF blocks on fused kernels; fp32, --channels 4, 8, 12 or 16, every "
-                         "size a multiple of 8, no --diff: its fields are always integrated; no --overlap-allreduce)")
-    ap.add_argument("--channels", type=int, default=16,
-                    help="--model rdn / rcn / pcnet: channels of the first encoder layer (the references' default; rcn runs 4 or 8)")
+                         "size a multiple of 8, no --diff: its fields are always integrated; no --overlap-allreduce), or the PR++ baseline "
+                         "(ReLU U-Net shared by both images, five correlation blocks, cross-grid flow composition; fp32, --channels a "
+                         "multiple of 4 up to 28, every size a multiple of 16, no --diff, no --overlap-allreduce)")
+    ap.add_argument("--channels", type=int, default=16, action=_Given,
+                    help="--model rdn / rcn / pcnet / prpp: channels of the first encoder layer (the references' default, 8 for prpp; "
+                         "rcn runs 4 or 8)")
     ap.add_argument("--cascades", type=int, default=10, help="--model rcn: number of cascaded VTNs (the reference's n_cascade)")
     ap.add_argument("--levels", default="1,1,1,1",
                     help="--model rdn: Estimator passes per level a,b,c,d, finest level first (the reference's level_recursion)")
@@ -157,6 +172,13 @@ def check_model_args(ap, args):
             ap.error("--diff is ModeT's and RDN's: the PCNet baseline integrates every field it composes as it is")
         if getattr(args, "overlap_allreduce", False):
             ap.error("--overlap-allreduce is ModeT's: the three-stage bucket cut follows ModeT's layers")
+    if args.model == "prpp":
+        if args.diff:
+            ap.error("--diff is ModeT's and RDN's: the PR++ baseline composes its fields without integration")
+        if getattr(args, "overlap_allreduce", False):
+            ap.error("--overlap-allreduce is ModeT's: the three-stage bucket cut follows ModeT's layers")
+        if not getattr(args, "channels_given", False):
+            args.channels = PRPP_CHANNELS
     return args
 
 
@@ -168,6 +190,8 @@ def make_model(args, img_size, training=False):
         return RCN(img_size, flow_multiplier=2, channels=args.channels, n_cascade=args.cascades, return_subflows=training)
     if args.model == "pcnet":                                   # "Baseline methods/PCnet/train.py":65
         return PCNet(img_size, channels=args.channels)
+    if args.model == "prpp":                                    # "Baseline methods/PR++/train.py":65
+        return PRNetplusplus(img_size, first_channel=args.channels)
     if args.model == "rdn":
         return RDN(img_size, channels=args.channels, level_recursion=rdn_levels(args), diff=args.diff, int_steps=args.int_steps)
     return ModeT(img_size, head_dim=6, num_heads=[8, 4, 2, 1, 1], scale=1, diff=args.diff, int_steps=args.int_steps)
@@ -183,6 +207,8 @@ def save_dir_name(args, num_heads, head_dim, weights):
         return "RCN_{}_{}_reg_{}{}_lr_{}_54r/".format(args.sim, weights[0], reg, weights[1], args.lr)
     if getattr(args, "model", "modet") == "pcnet":          # "Baseline methods/PCnet/train.py":49
         return "PCnet_{}_{}_reg_{}{}_lr_{}_54r/".format(args.sim, weights[0], reg, weights[1], args.lr)
+    if getattr(args, "model", "modet") == "prpp":           # "Baseline methods/PR++/train.py":49
+        return "PRNetplusplus_{}_{}_reg_{}{}_lr_{}_54r/".format(args.sim, weights[0], reg, weights[1], args.lr)
     diff = "_diff{}".format(args.int_steps) if getattr(args, "diff", False) else ""
     if getattr(args, "model", "modet") == "rdn":            # "Baseline methods/RDN/train.py":51 (its "diffusion" is the regulariser's weight)
         return "RDN({}, {}{}{}{})_{}_{}_diffusion_{}{}_lr_{}{}/".format(1, *rdn_levels(args), args.sim, weights[0], reg, weights[1], args.lr, diff)

@@ -59,8 +59,8 @@ def aten_dfi_gate(x, lg):
     return out
 
 
-def measure(leaves, consts, gy, fused, aten, algo_fwd, algo_bwd, steps):
-    """``leaves``: channels-last tensors both sides differentiate with respect to; ``consts``: further arguments; the ATen side
+def measure(leaves, consts, gy, fused, aten, algo_fwd, algo_bwd, steps, ref=None):
+    """``ref``: the composition evaluated in fp64 as the reference (default: ``aten`` itself).  ``leaves``: channels-last tensors both sides differentiate with respect to; ``consts``: further arguments; the ATen side
     returns a planar (B,C,D,H,W) result, compared with the fused side's channels-last one through a permuted view"""
     def fwd(fn):
         with torch.no_grad():
@@ -92,7 +92,7 @@ def measure(leaves, consts, gy, fused, aten, algo_fwd, algo_bwd, steps):
         r[leg]["aten_over_fused_peak"] = r[leg]["aten"]["peak_bytes"] / max(r[leg]["fused"]["peak_bytes"], 1)
     err = lambda got, want: float((got.double() - want).abs().max() / want.abs().max())      # noqa: E731
     l64 = [t.detach().double().requires_grad_(True) for t in leaves]
-    y64 = aten(*l64, *(c.double() for c in consts))
+    y64 = (ref or aten)(*l64, *(c.double() for c in consts))
     g64 = torch.autograd.grad(y64, l64, gy_p.double())
     r["error_vs_fp64"] = {"fused": {"y": err(planar(fwd(fused)), y64.detach())}, "aten": {"y": err(fwd(aten), y64.detach())}}
     for i, (f, a, want) in enumerate(zip(sides["fused"][1](), sides["aten"][1](), g64)):
