@@ -228,6 +228,12 @@ FAMILIES = {
         "modet_prpp_compose_fwd": (I, [P, P, P, I, I, I, I, I, I, I, P]),
         "modet_prpp_compose_bwd": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, I, I, P]),
     }),
+    "resize": (_header("modet_hip_resize.h"), {
+        "modet_resize_fwd": (I, [P, P, I, I, I, I, I, I, I, I, F, P]),
+        "modet_resize_bwd": (I, [P, P, I, I, I, I, I, I, I, I, F, P]),
+        "modet_resize_pyramid_fwd": (I, [P, P, P, P, I, I, I, I, P]),
+        "modet_resize_pyramid_bwd": (I, [P, P, P, P, P, I, I, I, I, P]),
+    }),
 }
 # The names a family's entry had before the registry.  Nothing in this tree uses them; they stay because the previous revision's
 # test files, which every change is also run against, reach the library through them (about 95 test ids).  Views of FAMILIES:

@@ -69,14 +69,15 @@ class Trainer:
 
     def _reg_fields(self, outs):
         """the model outputs the regulariser applies to: output [1], or -- a model that says ``reg_on_subflows`` (RCN, whose
-        reference loss, "Baseline methods/RCN/train.py":106-130, regularises every cascade's subflow and not the composed flow)
+        reference loss, "Baseline methods/RCN/train.py":106-130, regularises every cascade's subflow and not the composed flow;
+        RDNStages, whose reference loss regularises every stage field, "Baseline methods/RDN/train.py":104-130)
         -- every output [2:], each term weighted by ``weights[1]``"""
         if not getattr(self.model, "reg_on_subflows", False):
             _, flow = outs
             return [flow]
         if len(outs) < 3:
             raise RuntimeError(f"Trainer: {type(self.model).__name__} regularises its subflows (outputs [2:]): build it with "
-                               f"return_subflows=True")
+                               f"return_subflows=True (RCN) / return_stage_flows=True (RDNStages)")
         return list(outs[2:])
 
     def loss(self, moving, fixed):

@@ -6,6 +6,8 @@ fraction of voxels with non-positive Jacobian determinant; with --surface also H
     python -m smilecode_amd.infer --synthetic 3 --img-size 64,64,64            # random weights, no data needed
     python -m smilecode_amd.infer --synthetic 2 --img-size 32,32,32 --surface  # + one HD95 / ASSD line per pair and a summary
     python -m smilecode_amd.infer --model rdn --channels 16 --levels 1,1,1,1 --model-dir experiments/<run>/   # an RDN checkpoint
+    python -m smilecode_amd.infer --model rdn --stages 4 --levels 4,4,4,4 --model-dir experiments/<run>/      # the reference's RDN(4, 4444)
+    python -m smilecode_amd.infer --model rdn --stages 2 --share --model-dir experiments/<run>/               # an RDN_share checkpoint
     python -m smilecode_amd.infer --model rcn --channels 8 --cascades 10 --img-size 192,192,192 --model-dir experiments/<run>/   # an RCN checkpoint
     python -m smilecode_amd.infer --model pcnet --channels 16 --model-dir experiments/<run>/   # a PCNet checkpoint
     python -m smilecode_amd.infer --model prpp --channels 8 --model-dir experiments/<run>/     # a PR++ checkpoint
@@ -38,6 +40,8 @@ def make_parser():
                     help="--model rdn / rcn / pcnet / prpp: channels of the first encoder layer, as trained (prpp: 8 unless given)")
     ap.add_argument("--cascades", type=int, default=10, help="--model rcn: number of cascaded VTNs, as trained")
     ap.add_argument("--levels", default="1,1,1,1", help="--model rdn: Estimator passes per level a,b,c,d, finest level first, as trained")
+    ap.add_argument("--stages", type=int, default=1, help="--model rdn: number of recursive stages, as trained")
+    ap.add_argument("--share", action="store_true", help="--model rdn: the weight-shared RDN_share form, as trained")
     return ap
 
 

@@ -16,7 +16,9 @@ state_dict compatibility:
 
 ``Im2grid`` (the baseline of "Baseline methods/Im2Grid/models.py", further down) is built from the same launches plus the
 fused ``PositionalEncodingLayer``, with the same state_dict rules.  ``RDN`` (the baseline of "Baseline methods/RDN/models.py", at
-the end) adds the stride-2 encoder convolution (``ops.conv3d_s2``) and the Estimator on the stride-1 convolutions.  ``VTN`` / ``RCN``
+the end) adds the stride-2 encoder convolution (``ops.conv3d_s2``) and the Estimator on the stride-1 convolutions; ``RDNStages`` /
+``RDN_share`` run it at any ``stage_recursion`` on the trilinear flow pyramid (``ops.flow_pyramid``), ``ResizeTransform`` is
+``ops.resize``.  ``VTN`` / ``RCN``
 (the baseline of "Baseline methods/RCN/models.py", after it) add the stride-2 4x4x4 transposed convolution
 (``ops.conv_transpose3d_k4s2``) of the decoder.
 """
@@ -846,8 +848,8 @@ class RDN(nn.Module):
             raise RuntimeError(f"RDN: stage_recursion = {stage_recursion!r}: a positive integer")
         if stage_recursion > 1:
             raise RuntimeError(f"RDN: stage_recursion = {stage_recursion}: a second stage warps the features by the flow downsampled "
-                               f"trilinearly by 1/2, 1/4 and 1/8 (the reference's ResizeTransform / interpolate), which is not built; "
-                               f"only stage_recursion = 1 is supported")
+                               f"trilinearly by 1/2, 1/4 and 1/8 (the reference's ResizeTransform / interpolate), which this class "
+                               f"does not run: build RDNStages (or RDN_share) for stage_recursion > 1")
         levels = list(level_recursion)
         if len(levels) != 4 or any(isinstance(v, bool) or int(v) != v or v < 1 for v in levels):
             raise RuntimeError(f"RDN: level_recursion = {level_recursion}: four positive pass counts, finest level first")
@@ -899,44 +901,201 @@ class RDN(nn.Module):
         return self._run(moving, fixed, self.return_stage_flows)
 
     def _run(self, moving, fixed, stage_flows):
-        if moving.shape != fixed.shape or moving.dim() != 5:
-            raise RuntimeError("RDN.forward expects two (B,C,D,H,W) volumes of the same shape")
-        why = self.unsupported_shape(moving.shape[2:])
-        if why is not None:
-            raise RuntimeError("RDN.forward: " + why)
-        B = moving.shape[0]
-        mov_cl = ops.to_channels_last(moving.contiguous())
-        fix_cl = ops.to_channels_last(fixed.contiguous())
-        with ops.trace_range("encoder"):            # the shared encoder on both images as one batch (no layer mixes samples)
-            feats = self.encoder(ops.cat_batch(mov_cl, fix_cl))
-            M, Fx = zip(*(_SplitBatch.apply(f, B) for f in feats))
-        ST = self.transformer
-        ests = (self.est0[0], self.est1[0], self.est2[0], self.est3[0])
-        sflow = sv = None
-        for lvl in (3, 2, 1, 0):                    # features of level lvl sit on the grid of transformer[lvl + 1]
-            with ops.trace_range("level%d" % (lvl + 1)):
-                if sflow is not None:
-                    sflow = ops.upsample2(sflow, 2.0)
-                    if self.diff:
-                        sv = ops.upsample2(sv, 2.0)
-                for j in range(self.levels[lvl]):
-                    if sflow is None:               # level 4, first pass: no warp and no composition
-                        w = ests[lvl](Fx[lvl], M[lvl])
-                        sflow, sv = (self.integrate[lvl + 1].forward_cl(w), w) if self.diff else (w, None)
-                        continue
-                    # the stage flow has a second consumer (the composition): warp_tee adds that gradient in its own backward
-                    Mw, sflow = ops.warp_tee(M[lvl], sflow)
-                    w = ests[lvl](Fx[lvl], Mw)
-                    if self.diff:
-                        sv = ST[lvl + 1].forward_cl(sv, w, add_flow=True)
-                        w = self.integrate[lvl + 1].forward_cl(w)
-                    sflow = ST[lvl + 1].forward_cl(sflow, w, add_flow=True)
-        with ops.trace_range("output"):
-            flow_out = ops.upsample2(sflow, 2.0)
-            y_moved, flow_out = ops.warp_tee(mov_cl, flow_out)      # (the flow's other consumer: the caller, Grad3d in training)
+        mov_cl, M, Fx = _rdn_encode(self, "RDN", moving, fixed)
+        sflow, sv = _rdn_stage(self, (self.est0[0], self.est1[0], self.est2[0], self.est3[0]), Fx, M)
+        y_moved, flow_out = _rdn_output(mov_cl, sflow)
         if stage_flows:
             return y_moved, flow_out, (sv if self.diff else sflow)
         return y_moved, flow_out
+
+
+def _rdn_encode(model, name, moving, fixed):
+    """the channels-last moving volume and the four feature maps of either image, finest first (RDN and RDNStages)"""
+    if moving.shape != fixed.shape or moving.dim() != 5:
+        raise RuntimeError(f"{name}.forward expects two (B,C,D,H,W) volumes of the same shape")
+    why = RDN.unsupported_shape(moving.shape[2:])
+    if why is not None:
+        raise RuntimeError(f"{name}.forward: " + why)
+    B = moving.shape[0]
+    mov_cl = ops.to_channels_last(moving.contiguous())
+    fix_cl = ops.to_channels_last(fixed.contiguous())
+    with ops.trace_range("encoder"):            # the shared encoder on both images as one batch (no layer mixes samples)
+        feats = model.encoder(ops.cat_batch(mov_cl, fix_cl))
+        M, Fx = zip(*(_SplitBatch.apply(f, B) for f in feats))
+    return mov_cl, M, Fx
+
+
+def _rdn_stage(model, ests, Fx, Fm):
+    """one stage of RDN ("Baseline methods/RDN/models.py":488-514, :379-419): the four levels, coarsest first, over the fixed
+    features Fx and this stage's moving features Fm; ests = the stage's Estimators, finest first.  Returns (sflow, sv), the stage
+    field on the half-resolution grid and (``diff``) its composed velocity."""
+    ST = model.transformer
+    sflow = sv = None
+    for lvl in (3, 2, 1, 0):                    # features of level lvl sit on the grid of transformer[lvl + 1]
+        with ops.trace_range("level%d" % (lvl + 1)):
+            if sflow is not None:
+                sflow = ops.upsample2(sflow, 2.0)
+                if model.diff:
+                    sv = ops.upsample2(sv, 2.0)
+            for j in range(model.levels[lvl]):
+                if sflow is None:               # level 4, first pass: no warp and no composition
+                    w = ests[lvl](Fx[lvl], Fm[lvl])
+                    sflow, sv = (model.integrate[lvl + 1].forward_cl(w), w) if model.diff else (w, None)
+                    continue
+                # the stage flow has a second consumer (the composition): warp_tee adds that gradient in its own backward
+                Mw, sflow = ops.warp_tee(Fm[lvl], sflow)
+                w = ests[lvl](Fx[lvl], Mw)
+                if model.diff:
+                    sv = ST[lvl + 1].forward_cl(sv, w, add_flow=True)
+                    w = model.integrate[lvl + 1].forward_cl(w)
+                sflow = ST[lvl + 1].forward_cl(sflow, w, add_flow=True)
+    return sflow, sv
+
+
+def _rdn_output(mov_cl, flow):
+    """(y_moved, flow_out) from the half-resolution flow"""
+    with ops.trace_range("output"):
+        flow_out = ops.upsample2(flow, 2.0)
+        return ops.warp_tee(mov_cl, flow_out)       # (the flow's other consumer: the caller, Grad3d in training)
+
+
+class ResizeTransform(nn.Module):
+    """The reference's ResizeTransform ("Baseline methods/RDN/models.py":91-117): resizes a vector field trilinearly
+    (align_corners=True) to floor(S * factor) along every axis and multiplies it by ``factor``, planar (B,C,D,H,W) in and out;
+    ``forward_cl`` takes and returns channels-last.  ``factor == 1`` returns its input.  One kernel in either direction
+    (ops.resize); its backward is a gather.  The reference scales after resizing for ``factor < 1`` and before for ``factor > 1``;
+    the kernel always scales after.  The difference is rounding only, and there is none where ``factor`` is a power of two."""
+
+    def __init__(self, factor, ndims=3):
+        super().__init__()
+        if ndims != 3:
+            raise RuntimeError(f"ResizeTransform: ndims = {ndims!r}: only the trilinear (ndims = 3) resize is built")
+        if isinstance(factor, bool) or not isinstance(factor, (int, float)) or not factor > 0 or not math.isfinite(factor):
+            raise RuntimeError(f"ResizeTransform: factor = {factor!r}: a positive finite number")
+        self.factor = factor
+        self.mode = "trilinear"
+
+    def _size(self, shape):
+        size = tuple(int(math.floor(float(s) * self.factor)) for s in shape)
+        if min(size) < 1:
+            raise RuntimeError(f"ResizeTransform: factor = {self.factor} leaves a size of 0: {tuple(shape)} -> {size}")
+        return size
+
+    def forward(self, x):
+        if self.factor == 1:
+            return x
+        if x.dim() != 5:
+            raise RuntimeError(f"ResizeTransform.forward expects a (B,C,D,H,W) field, got {tuple(x.shape)}")
+        self._size(x.shape[2:])
+        return ops.to_ncdhw(self.forward_cl(ops.to_channels_last(x.contiguous())))
+
+    def forward_cl(self, x_cl):
+        if self.factor == 1:
+            return x_cl
+        if x_cl.dim() != 5:
+            raise RuntimeError(f"ResizeTransform.forward_cl expects a (B,D,H,W,C) field, got {tuple(x_cl.shape)}")
+        return ops.resize(x_cl, self._size(x_cl.shape[1:4]), float(self.factor))
+
+
+class RDNStages(nn.Module):
+    """RDN at ANY ``stage_recursion``, and its weight-shared forms.  With ``share=False`` the reference's RDN / RDN_test
+    ("Baseline methods/RDN/models.py":434-615) and, ``diff=True``, RDN_diff / RDN_diff_test (:323-432, :884-978), state-dict keys
+    ``estN.<stage>.conv.{0,1,2,4}.*``; with ``share=True`` RDN_share / RDN_share_test and RDN_diff_share / RDN_diff_share_test
+    (:217-321, :617-704): one Estimator per level, reused by every stage, keys ``estN.conv.*``.  Stage 0 is ``RDN``'s one stage.
+    From stage 1 on the moving features are warped by the flow so far, the three coarser maps by its rescaled trilinear
+    downsamplings (ops.flow_pyramid: one launch forward, one backward), and the stage's field is composed with the flow,
+    ``flow = ST(flow, sflow) + sflow``.  ``forward(moving, fixed)`` returns ``(y_moved, flow_out)``, with
+    ``return_stage_flows=True`` the reference's training tuple ``(y_moved, flow_out, *sflows)`` (``*svs`` with ``diff``): 2 +
+    stages outputs.  The regulariser of the reference's train loop ("Baseline methods/RDN/train.py":104-130) applies to every
+    stage field.  With ``stage_recursion=1, share=False`` the results and gradients are ``RDN``'s bit for bit: the same launches
+    in the same order.  fp32 only."""
+
+    stage_buckets = False       # engine.Trainer: the three-stage bucket cut of the overlapped all-reduce is ModeT's
+    reg_on_subflows = True      # engine.Trainer: the regulariser applies to every output [2:] (the stage fields), not to output [1]
+
+    def __init__(self, inshape=(160, 192, 160), in_channel=1, channels=16, stage_recursion=1, level_recursion=[1, 1, 1, 1],
+                 diff=False, int_steps=7, share=False, return_stage_flows=False, legacy_grid_buffers=False,
+                 act_dtype=torch.float32):
+        super().__init__()
+        name = type(self).__name__
+        if act_dtype != torch.float32:
+            raise RuntimeError(f"{name}: act_dtype = {act_dtype}: the stride-2 convolution kernels are fp32 only (bf16 storage is ModeT's)")
+        if isinstance(stage_recursion, bool) or not isinstance(stage_recursion, int) or stage_recursion < 1:
+            raise RuntimeError(f"{name}: stage_recursion = {stage_recursion!r}: a positive integer")
+        levels = list(level_recursion)
+        if len(levels) != 4 or any(isinstance(v, bool) or int(v) != v or v < 1 for v in levels):
+            raise RuntimeError(f"{name}: level_recursion = {level_recursion}: four positive pass counts, finest level first")
+        why = RDN.unsupported_shape(inshape)
+        if why is not None:
+            raise RuntimeError(f"{name}: inshape: " + why)
+        why = rdn_unsupported_config(in_channel, channels)
+        if why is not None:
+            raise RuntimeError(f"{name}: " + why)
+        self.channels = channels
+        self.step = 7
+        self.inshape = tuple(int(s) for s in inshape)
+        self.stages = stage_recursion
+        self.levels = [int(v) for v in levels]
+        self.diff = bool(diff)
+        self.share = bool(share)
+        self.int_steps = int_steps
+        self.return_stage_flows = bool(return_stage_flows)
+        self.act_dtype = act_dtype
+        c = channels
+        self.encoder = EncoderS2(in_channel=in_channel, first_out_channel=c)
+        for lvl, width in ((3, 8), (2, 4), (1, 2), (0, 1)):
+            est = Estimator(2 * width * c) if self.share else nn.ModuleList([Estimator(2 * width * c) for _ in range(self.stages)])
+            setattr(self, "est%d" % lvl, est)
+        self.transformer = nn.ModuleList(
+            [SpatialTransformer([s // 2 ** i for s in self.inshape], legacy_grid_buffers=legacy_grid_buffers) for i in range(5)])
+        if self.diff:
+            self.integrate = nn.ModuleList(
+                [VecInt([s // 2 ** i for s in self.inshape], int_steps, legacy_grid_buffers=legacy_grid_buffers) for i in range(5)])
+
+    unsupported_shape = staticmethod(RDN.unsupported_shape)
+
+    def forward(self, moving, fixed):
+        """(y_moved (B,1,D,H,W), flow_out (B,3,D,H,W)[, one field (B,3,D/2,H/2,W/2) per stage])"""
+        return tuple(ops.to_ncdhw(t) for t in self._run(moving, fixed, self.return_stage_flows))
+
+    def forward_cl(self, moving, fixed):
+        """``forward`` with the results channels-last, as the kernels wrote them"""
+        return self._run(moving, fixed, self.return_stage_flows)
+
+    def _estimators(self, i):
+        ests = (self.est0, self.est1, self.est2, self.est3)
+        return ests if self.share else tuple(e[i] for e in ests)
+
+    def _run(self, moving, fixed, stage_flows):
+        mov_cl, M, Fx = _rdn_encode(self, type(self).__name__, moving, fixed)
+        ST = self.transformer
+        flow, fields = None, []
+        for i in range(self.stages):
+            if i == 0:
+                Fm = M
+            else:
+                with ops.trace_range("stage%d_warp" % i):
+                    # the flow so far has three consumers in this stage: warp_tee folds the gradients of the other two (the
+                    # pyramid and the closing composition, which take the returned alias) into its own backward
+                    Fm0, flow = ops.warp_tee(M[0], flow)
+                    f2, f4, f8 = ops.flow_pyramid(flow)
+                    Fm = (Fm0, ST[2].forward_cl(M[1], f2), ST[3].forward_cl(M[2], f4), ST[4].forward_cl(M[3], f8))
+            sflow, sv = _rdn_stage(self, self._estimators(i), Fx, Fm)
+            flow = sflow if i == 0 else ST[1].forward_cl(flow, sflow, add_flow=True)
+            fields.append(sv if self.diff else sflow)
+        y_moved, flow_out = _rdn_output(mov_cl, flow)
+        if stage_flows:
+            return (y_moved, flow_out) + tuple(fields)
+        return y_moved, flow_out
+
+
+class RDN_share(RDNStages):
+    """``RDNStages(share=True)`` under the reference's name ("Baseline methods/RDN/models.py":617-704; ``diff=True``: RDN_diff_share)"""
+
+    def __init__(self, inshape=(160, 192, 160), in_channel=1, channels=16, stage_recursion=1, level_recursion=[1, 1, 1, 1],
+                 diff=False, int_steps=7, return_stage_flows=False, legacy_grid_buffers=False, act_dtype=torch.float32):
+        super().__init__(inshape, in_channel, channels, stage_recursion, level_recursion, diff=diff, int_steps=int_steps, share=True,
+                         return_stage_flows=return_stage_flows, legacy_grid_buffers=legacy_grid_buffers, act_dtype=act_dtype)
 
 
 class _ConvTranspose3dParams(nn.Module):

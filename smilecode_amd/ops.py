@@ -2287,6 +2287,105 @@ def compose_cross(src, w):
     return _ComposeCross.apply(src, w)
 
 
+# ---- the resize family (include/modet_hip_resize.h): trilinear resizing between any two grids, and a stage's flow pyramid
+RESIZE_MAX_CHANNELS = 256        # MODET_RESIZE_MAX_C of include/modet_hip_resize.h
+PYRAMID_MIN_SIZE = 8             # MODET_RESIZE_PYRAMID_MIN: the 1/8 output then has one voxel along that axis
+_PYRAMID = ((2, 0.5), (4, 0.25), (8, 0.125))
+
+
+def _resize_args(op, x, size, scale):
+    _chk(x)
+    _rank5(op, "x", x)
+    size = tuple(size)
+    if len(size) != 3 or any(isinstance(s, bool) or int(s) != s or s < 1 for s in size):
+        raise RuntimeError(f"{op}: size {size!r} must be three positive integers (D, H, W)")
+    B, D, H, W, C = x.shape
+    if B < 1 or min(D, H, W) < 1:
+        raise RuntimeError(f"{op}: x {tuple(x.shape)} is empty")
+    if B > 65535 or not 1 <= C <= RESIZE_MAX_CHANNELS:
+        raise RuntimeError(f"{op}: x {tuple(x.shape)}: the kernels take up to 65535 samples and 1 to {RESIZE_MAX_CHANNELS} channels")
+    if not math.isfinite(scale):
+        raise RuntimeError(f"{op}: scale = {scale!r} must be finite")
+    return (B, D, H, W) + tuple(int(s) for s in size) + (C,)
+
+
+class _Resize(Function):
+    @staticmethod
+    def forward(ctx, x, size, scale):
+        dims = _resize_args("resize", x, size, scale)
+        B, C = dims[0], dims[-1]
+        y = torch.empty((B,) + dims[4:7] + (C,), dtype=torch.float32, device=x.device)
+        with _Guard(x, f"resize_fwd[C{C}]", 16.0 * y.numel(), 4.0 * (x.numel() + y.numel())):
+            _call(_L().modet_resize_fwd, _p(x), _p(y), *dims, float(scale), _stream())
+        ctx.dims, ctx.scale = dims, float(scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dims = ctx.dims
+        dy = dy.contiguous()
+        dx = torch.empty((dims[0],) + dims[1:4] + (dims[-1],), dtype=torch.float32, device=dy.device)
+        with _Guard(dy, f"resize_bwd[C{dims[-1]}]", 16.0 * dy.numel(), 4.0 * (dx.numel() + dy.numel())):
+            _call(_L().modet_resize_bwd, _p(dy), _p(dx), *dims, ctx.scale, _stream())
+        return dx, None, None
+
+
+def resize(x, size, scale=1.0):
+    """scale * F.interpolate(x, size=size, mode='trilinear', align_corners=True) of a channels-last (B,D,H,W,C) volume onto ANY
+    (D', H', W'): down, up or identity, per axis (the reference's ResizeTransform, "Baseline methods/RDN/models.py":91-117).  The
+    backward is a gather: no atomics, bit-reproducible."""
+    return _Resize.apply(x, size, scale)
+
+
+def flow_pyramid_sizes(D, H, W):
+    """the three output grids of flow_pyramid: floor(S / 2), floor(S / 4), floor(S / 8), as nnf.interpolate(scale_factor=) sizes them"""
+    return tuple((D // f, H // f, W // f) for f, _ in _PYRAMID)
+
+
+class _FlowPyramid(Function):
+    """one node with three outputs: the forward reads the field once, the backward is ONE gather launch over whichever
+    cotangents arrived (an output nobody differentiates is passed as NULL)"""
+
+    @staticmethod
+    def forward(ctx, flow):
+        op = "flow_pyramid"
+        _chk(flow)
+        _rank5(op, "flow", flow)
+        B, D, H, W, C = flow.shape
+        if C != 3:
+            raise RuntimeError(f"{op}: flow {tuple(flow.shape)} must have 3 channels (a displacement field)")
+        if not 1 <= B <= 65535 or min(D, H, W) < PYRAMID_MIN_SIZE:
+            raise RuntimeError(f"{op}: flow {tuple(flow.shape)} needs 1 to 65535 samples and at least {PYRAMID_MIN_SIZE} voxels along "
+                               "every axis (the 1/8 grid would be empty)")
+        ys = tuple(torch.empty((B,) + s + (3,), dtype=torch.float32, device=flow.device) for s in flow_pyramid_sizes(D, H, W))
+        nout = sum(y.numel() for y in ys)
+        with _Guard(flow, "flow_pyramid_fwd", 16.0 * nout, 4.0 * (flow.numel() + nout)):
+            _call(_L().modet_resize_pyramid_fwd, _p(flow), _p(ys[0]), _p(ys[1]), _p(ys[2]), B, D, H, W, _stream())
+        ctx.dims = (B, D, H, W)
+        ctx.set_materialize_grads(False)
+        return ys
+
+    @staticmethod
+    def backward(ctx, d2, d4, d8):
+        gs = [None if g is None else g.contiguous() for g in (d2, d4, d8)]
+        if all(g is None for g in gs):
+            return None
+        ref = next(g for g in gs if g is not None)
+        B, D, H, W = ctx.dims
+        dx = torch.empty((B, D, H, W, 3), dtype=torch.float32, device=ref.device)
+        nin = sum(g.numel() for g in gs if g is not None)
+        with _Guard(ref, "flow_pyramid_bwd", 16.0 * nin, 4.0 * (dx.numel() + nin)):
+            _call(_L().modet_resize_pyramid_bwd, _p(gs[0]), _p(gs[1]), _p(gs[2]), None, _p(dx), B, D, H, W, _stream())
+        return dx
+
+
+def flow_pyramid(flow):
+    """(0.5 resize(flow, S // 2), 0.25 resize(flow, S // 4), 0.125 resize(flow, S // 8)) of a channels-last field (B,D,H,W,3): the
+    three rescaled trilinear downsamplings a recursive RDN stage warps its coarser features by ("Baseline methods/RDN/models.py":
+    480-486), from one launch; each output holds the bits of ``resize`` at the same size and scale.  One launch backwards too."""
+    return _FlowPyramid.apply(flow)
+
+
 class _ToCL(Function):
     @staticmethod
     def forward(ctx, x):

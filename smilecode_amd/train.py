@@ -25,7 +25,7 @@ import torch
 from . import data, utils
 from .engine import Trainer, poly_lr
 from .losses import REG_TERMS, SIM_TERMS
-from .models import RCN, RDN, Im2grid, ModeT, PCNet, PRNetplusplus
+from .models import RCN, RDN, Im2grid, ModeT, PCNet, PRNetplusplus, RDNStages
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
 
@@ -123,7 +123,8 @@ def make_parser():
     ap.add_argument("--model", choices=MODELS, default="modet",
                     help="the network: ModeT, or the Im2Grid baseline the paper compares it with (positional-encoding projection + "
                          "coordinate translator per level; fp32, no --diff, no --overlap-allreduce), or the RDN baseline (stride-2 "
-                         "encoder, one Estimator per level; fp32, one stage, --diff = its RDN_diff form, no --overlap-allreduce), or the RCN "
+                         "encoder, one Estimator per level and stage; fp32, --stages recursive stages, --share = its RDN_share form, --diff = its "
+                         "RDN_diff form, no --overlap-allreduce; from two stages on the regulariser applies to every stage field), or the RCN "
                          "baseline (--cascades VTNs on stride-2 and transposed convolutions, flow_multiplier 2; fp32, --channels 4 or 8, every "
                          "size a multiple of 64, no --diff, no --overlap-allreduce; the regulariser applies to every cascade's subflow), or the "
                          "PCNet baseline (two residual encoders, DFI and NFF blocks on fused kernels; fp32, --channels 4, 8, 12 or 16, every "
@@ -136,6 +137,10 @@ def make_parser():
     ap.add_argument("--cascades", type=int, default=10, help="--model rcn: number of cascaded VTNs (the reference's n_cascade)")
     ap.add_argument("--levels", default="1,1,1,1",
                     help="--model rdn: Estimator passes per level a,b,c,d, finest level first (the reference's level_recursion)")
+    ap.add_argument("--stages", type=int, default=1,
+                    help="--model rdn: number of recursive stages (the reference's stage_recursion; its train.py runs 4 with --levels 4,4,4,4)")
+    ap.add_argument("--share", action="store_true",
+                    help="--model rdn: one Estimator per level shared by every stage (the reference's RDN_share; with --diff RDN_diff_share)")
     return ap
 
 
@@ -150,6 +155,8 @@ def rdn_levels(args):
 
 def check_model_args(ap, args):
     """argument combinations a network does not have end as argument errors, before anything is built"""
+    if args.model != "rdn" and (getattr(args, "stages", 1) != 1 or getattr(args, "share", False)):
+        ap.error("--stages and --share are RDN's (--model rdn): no other network has recursive stages")
     if args.model == "im2grid":
         if args.diff:
             ap.error("--diff is ModeT's: the Im2Grid baseline composes its fields without integration")
@@ -160,6 +167,8 @@ def check_model_args(ap, args):
             ap.error("--overlap-allreduce is ModeT's: the three-stage bucket cut follows ModeT's layers")
         if rdn_levels(args) is None:
             ap.error("--levels takes four positive pass counts a,b,c,d (finest level first), got {!r}".format(args.levels))
+        if getattr(args, "stages", 1) < 1:
+            ap.error("--stages takes a positive number of stages, got {!r}".format(args.stages))
     if args.model == "rcn":
         if args.diff:
             ap.error("--diff is ModeT's and RDN's: the RCN baseline composes its subflows without integration")
@@ -193,7 +202,12 @@ def make_model(args, img_size, training=False):
     if args.model == "prpp":                                    # "Baseline methods/PR++/train.py":65
         return PRNetplusplus(img_size, first_channel=args.channels)
     if args.model == "rdn":
-        return RDN(img_size, channels=args.channels, level_recursion=rdn_levels(args), diff=args.diff, int_steps=args.int_steps)
+        stages, share = getattr(args, "stages", 1), getattr(args, "share", False)
+        if stages == 1 and not share:
+            return RDN(img_size, channels=args.channels, level_recursion=rdn_levels(args), diff=args.diff, int_steps=args.int_steps)
+        # "Baseline methods/RDN/train.py":49-67; its loss regularises every stage field, so training needs them all
+        return RDNStages(img_size, channels=args.channels, stage_recursion=stages, level_recursion=rdn_levels(args), diff=args.diff,
+                         int_steps=args.int_steps, share=share, return_stage_flows=training)
     return ModeT(img_size, head_dim=6, num_heads=[8, 4, 2, 1, 1], scale=1, diff=args.diff, int_steps=args.int_steps)
 
 
@@ -211,7 +225,8 @@ def save_dir_name(args, num_heads, head_dim, weights):
         return "PRNetplusplus_{}_{}_reg_{}{}_lr_{}_54r/".format(args.sim, weights[0], reg, weights[1], args.lr)
     diff = "_diff{}".format(args.int_steps) if getattr(args, "diff", False) else ""
     if getattr(args, "model", "modet") == "rdn":            # "Baseline methods/RDN/train.py":51 (its "diffusion" is the regulariser's weight)
-        return "RDN({}, {}{}{}{})_{}_{}_diffusion_{}{}_lr_{}{}/".format(1, *rdn_levels(args), args.sim, weights[0], reg, weights[1], args.lr, diff)
+        return "RDN{}({}, {}{}{}{})_{}_{}_diffusion_{}{}_lr_{}{}/".format("_share" if getattr(args, "share", False) else "", getattr(args, "stages", 1),
+                                                                          *rdn_levels(args), args.sim, weights[0], reg, weights[1], args.lr, diff)
     return "modet-heads({}{}{}{}{})-rpe_headim_{}_{}_{}_reg_{}{}_lr_{}_54r{}/".format(*num_heads, head_dim, args.sim, weights[0], reg,
                                                                                      weights[1], args.lr, diff)
 
