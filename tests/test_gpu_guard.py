@@ -414,6 +414,12 @@ CASES = {
     "conv_q[16->32,9x17x28,B2]": conv_case(16, 32, (9, 17, 28), 2),
     "conv_q[64->64,8x9x30,B2]": conv_case(64, 64, (8, 9, 30), 2),
     "conv_q[2->12,12x18x21]": conv_case(2, 12, (12, 18, 21), 1),
+    # exact-f32 MFMA on odd channel counts (tests/test_gpu_conv_exact.py): scalar loads, ragged channel stages and N tiles,
+    # 2 and 4 output rows packed into N; the weight gradients of 43->43 and 3->16 are the exact-f32 kernel's too
+    "conv_exact[43->43,act,9x11x37,B2]": conv_case(43, 43, (9, 11, 37), 2, act=True),
+    "conv_exact[43->8,act,17x43x45,B2]": conv_case(43, 8, (17, 43, 45), 2, act=True),
+    "conv_exact[16->3,act,17x43x45,B2]": conv_case(16, 3, (17, 43, 45), 2, act=True),
+    "conv_exact[3->16,act,17x43x45,B2]": conv_case(3, 16, (17, 43, 45), 2, act=True),
     "conv_stats[8->16,6x8x16]": conv_case(8, 16, (6, 8, 16), 1, form="stats", x_act=True),
     "conv_stats[32->32,4x6x9]": conv_case(32, 32, (4, 6, 9), 2, form="stats"),
     "conv_ins[4->8,9x24x37]": conv_case(4, 8, (9, 24, 37), 1, form="ins"),
