@@ -234,6 +234,11 @@ FAMILIES = {
         "modet_resize_pyramid_fwd": (I, [P, P, P, P, I, I, I, I, P]),
         "modet_resize_pyramid_bwd": (I, [P, P, P, P, P, I, I, I, I, P]),
     }),
+    "segdice": (_header("modet_hip_segdice.h"), {
+        "modet_segdice_ws_bytes": (SZ, [I, I, I, I, I]),
+        "modet_segdice_sums": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, P]),
+        "modet_segdice_fwd_bwd": (I, [P, P, P, P, P, P, P, SZ, I, I, I, I, I, I, F, I, P]),
+    }),
 }
 # The names a family's entry had before the registry.  Nothing in this tree uses them; they stay because the previous revision's
 # test files, which every change is also run against, reach the library through them (about 95 test ids).  Views of FAMILIES:

@@ -26,13 +26,17 @@ def poly_lr(epoch, max_epoch=30, init_lr=1e-4, power=0.9):
 
 class Trainer:
     def __init__(self, model, lr=1e-4, max_epoch=30, weights=(1.0, 1.0), betas=(0.9, 0.999), eps=1e-8, group=None,
-                 overlap_allreduce=False, sim=None, reg=None):
+                 overlap_allreduce=False, sim=None, reg=None, seg=None, seg_weight=1.0):
         """``sim``: the similarity term, called as ``sim(fixed, y_moved)``; None = ``NCC_vxm()`` (the reference's train.py:103),
         ``losses.MIND_loss()``, ``losses.MutualInformation()`` or ``losses.localMutualInformation()`` for multi-modal pairs,
         ``losses.SSIM3D()``, or any module (one the step does not know runs through autograd).
         ``reg``: the flow regulariser, called as ``reg(flow, fixed)``; None = ``Grad3d(penalty="l2")`` (the reference's
         train.py:104), ``losses.Grad3DiTV()``, ``losses.DisplacementRegularizer('bending' | 'gradient-l2' | 'gradient-l1')``, or
         any module, as for ``sim``.
+        ``seg``: a label-overlap term of weakly supervised training, called as ``seg(flow, moving_labels, fixed_labels)`` on the
+        model's composed flow (output [1]) and added with the weight ``seg_weight``: ``losses.LabelDice(nlabels)`` or any module;
+        None = no such term, and nothing about the step changes.  With it every step takes ``labels = (moving_labels,
+        fixed_labels)``, two (B,1,D,H,W) int16 maps, and returns ``(loss, sim, reg, seg)``.  Not with ``overlap_allreduce``.
         ``overlap_allreduce``: all-reduce the gradients in three buckets while the rest of the backward runs
         (BASELINE.json configs[4]).  The backward is cut into THREE AUTOGRAD STAGES at the bucket boundaries
         (parallel.MODET_BUCKETS: per-level heads | encoder levels 3-5 | encoder levels 1-2; cut tensors = the encoder's
@@ -44,6 +48,9 @@ class Trainer:
         if overlap_allreduce and not getattr(model, "stage_buckets", True):
             raise RuntimeError(f"Trainer: overlap_allreduce=True cuts the backward at ModeT's three bucket boundaries "
                                f"(parallel.MODET_BUCKETS); {type(model).__name__} has no such cut: train it with the plain all-reduce")
+        if seg is not None and overlap_allreduce:
+            raise RuntimeError("Trainer: seg (a label-overlap term) is not built into the staged step of overlap_allreduce=True: "
+                               "train it with the plain all-reduce")
         self.model = model
         self.lr0, self.max_epoch, self.weights = lr, max_epoch, weights
         self.betas, self.eps, self.group = betas, eps, group
@@ -62,6 +69,8 @@ class Trainer:
         self.lr_last = lr
         self.sim = NCC_vxm() if sim is None else sim
         self.reg = Grad3d(penalty="l2") if reg is None else reg
+        self.seg, self.seg_weight = seg, float(seg_weight)
+        self._static_labels = None          # the captured step's two label buffers (seg)
         self.buckets = None
         if overlap_allreduce:
             from .parallel import MODET_BUCKETS, BucketedAllReduce
@@ -80,7 +89,18 @@ class Trainer:
                                f"return_subflows=True (RCN) / return_stage_flows=True (RDNStages)")
         return list(outs[2:])
 
-    def loss(self, moving, fixed):
+    def _labels(self, labels, where):
+        """the label pair of a step: present exactly when the trainer has a ``seg`` term"""
+        if self.seg is None:
+            if labels is not None:
+                raise RuntimeError(f"Trainer.{where}: labels were given but the trainer has no seg term (Trainer(seg=...))")
+            return None
+        if labels is None or len(labels) != 2:
+            raise RuntimeError(f"Trainer.{where}: the seg term needs labels=(moving_labels, fixed_labels)")
+        return labels
+
+    def loss(self, moving, fixed, labels=None):
+        labels = self._labels(labels, "loss")
         outs = self.model(moving, fixed)
         y_moved, fields = outs[0], self._reg_fields(outs)
         sim = self.sim(fixed, y_moved)
@@ -91,6 +111,11 @@ class Trainer:
             sim = sim * self.weights[0]     # multiplication is a 4 us launch forward and another one backward
         if self.weights[1] != 1.0:
             reg = reg * self.weights[1]
+        if labels is not None:
+            seg = self.seg(outs[1], labels[0], labels[1])
+            if self.seg_weight != 1.0:
+                seg = seg * self.seg_weight
+            return sim + reg + seg, sim, reg, seg
         return sim + reg, sim, reg
 
     def _seedable(self):
@@ -100,9 +125,9 @@ class Trainer:
         expression) on a model that hands out its channels-last results"""
         if not (self.seed_backward and hasattr(self.model, "forward_cl")):
             return False
-        return seeds(self.sim) and seeds(self.reg)
+        return seeds(self.sim) and seeds(self.reg) and (self.seg is None or seeds(self.seg))
 
-    def _seeded_loss(self, moving, fixed):
+    def _seeded_loss(self, moving, fixed, labels=None):
         """``loss`` for the step itself: ((loss, sim, reg) detached, roots, seeds) with ``seeds[i]`` = d loss / d ``roots[i]``
         -- the two loss kernels write value AND weighted gradient in one call (they always did: the autograd nodes of
         ops.ncc_loss / ops.grad3d_loss save the gradient in forward and multiply it by the upstream scalar in backward), so the
@@ -125,25 +150,38 @@ class Trainer:
             sim = sim * w0
         if w1 != 1.0:
             reg = reg * w1
-        return (sim + reg, sim, reg), [y_cl] + fields, [d_y.reshape(y_cl.shape)] + d_fields
+        roots, grads = [y_cl] + fields, [d_y.reshape(y_cl.shape)] + d_fields
+        if labels is None:
+            return (sim + reg, sim, reg), roots, grads
+        # the label term on the composed flow: where that is the regularised field its seed is ADDED into the regulariser's (no
+        # further pass, no further root); a model with reg_on_subflows gets the composed flow as one more root
+        ws = self.seg_weight
+        if fields[0] is outs[1]:
+            seg, _ = self.seg.value_and_grad_cl(outs[1].detach(), labels[0], labels[1], ws, d_flow_add=d_flow)
+        else:
+            seg, d_seg = self.seg.value_and_grad_cl(outs[1].detach(), labels[0], labels[1], ws)
+            roots, grads = roots + [outs[1]], grads + [d_seg]
+        if ws != 1.0:
+            seg = seg * ws
+        return (sim + reg + seg, sim, reg, seg), roots, grads
 
     # ---------------------------------------------------------------- hipGraph replay of forward + backward
-    def _fwd_bwd(self, moving, fixed):
+    def _fwd_bwd(self, moving, fixed, labels=None):
         self.fp.zero_grad()
         seeded = self._seedable()
         if not self.batch_small_launches:               # MODET_STEP_BATCHING=0: every conv packs / reduces on its own (A/B)
             with ops.trace_range("forward+loss"):
                 if seeded:
-                    (loss, sim, reg), roots, seeds = self._seeded_loss(moving, fixed)
+                    vals, roots, seeds = self._seeded_loss(moving, fixed, labels)
                 else:
-                    loss, sim, reg = self.loss(moving, fixed)
+                    vals = self.loss(moving, fixed, labels)
             with ops.trace_range("backward"):
                 if seeded:
                     torch.autograd.backward(roots, seeds)
                 else:
-                    loss.backward()
+                    vals[0].backward()
                 self.fp.gather_grads()
-            return loss.detach(), sim.detach(), reg.detach()
+            return tuple(v.detach() for v in vals)
         # one caller-owned step context per computation this trainer has run (shape, device, grad mode): its recorded
         # packing jobs and its packed-weights arena stay valid for as long as the trainer lives, so a captured graph of
         # shape A keeps working however many other shapes run eagerly in between
@@ -152,18 +190,18 @@ class Trainer:
         with sc.prepacked():
             with ops.trace_range("forward+loss"):
                 if seeded:
-                    (loss, sim, reg), roots, seeds = self._seeded_loss(moving, fixed)
+                    vals, roots, seeds = self._seeded_loss(moving, fixed, labels)
                 else:
-                    loss, sim, reg = self.loss(moving, fixed)
+                    vals = self.loss(moving, fixed, labels)
             with ops.trace_range("backward"):
                 # the ~20 per-layer partial-tile reductions as one launch, written straight into the flat gradient buffer
                 with sc.deferred(self.fp.grad_destinations()) as scope:
                     if seeded:
                         torch.autograd.backward(roots, seeds)
                     else:
-                        loss.backward()
+                        vals[0].backward()
                 self.fp.gather_grads(scope.written)
-        return loss.detach(), sim.detach(), reg.detach()
+        return tuple(v.detach() for v in vals)
 
     # ---------------------------------------------------------------- backward in three stages (overlapped all-reduce)
     def _step_context(self, moving):
@@ -351,7 +389,7 @@ class Trainer:
                 fail(rep, f"{len(bad)} of {nseg} parameter tensors differ, first #{i} {names[i]}{where} (|diff|_2 "
                           f"{float(err_sq[i]) ** 0.5:.3e} vs |grad|_2 {float(ref_sq[i]) ** 0.5:.3e}, bound {rel:g})")
 
-    def capture(self, moving, fixed, warmup=2, verify=True):
+    def capture(self, moving, fixed, warmup=2, verify=True, labels=None):
         """Capture forward + losses + backward + gradient packing for this input shape into ONE hipGraph
         (torch.cuda.CUDAGraph = hipGraph on ROCm).  A step is ~500 kernel launches issued from Python through ctypes and
         the autograd tape (6-7 ms of host time at 160x192x160); replaying the graph costs the host ~0.1 ms, so the GPU
@@ -362,19 +400,23 @@ class Trainer:
         parameters.  ``verify``: the captured step is replayed TWICE and its gradients compared with the eager step's
         before the graph is accepted (RuntimeError otherwise) -- a captured stream operation that is not a kernel may replay
         differently from how it ran (round 3: a hipMemsetAsync node cleared its buffer on the first replay only and the step
-        was silently wrong from the second one on); two eager-sized steps, once per capture.  Returns self."""
+        was silently wrong from the second one on); two eager-sized steps, once per capture.  ``labels``: the label pair of a
+        trainer with a ``seg`` term; the graph reads two static label buffers that every step refreshes like the images.
+        Returns self."""
+        labels = self._labels(labels, "capture")
         self.model.train()
         if self.buckets is not None:
             self._capture_staged(moving, fixed, warmup, verify)
             return self
         self._static_in = self._static_pair(moving, fixed)
+        self._static_labels = None if labels is None else tuple(t.clone() for t in labels)
         side = torch.cuda.Stream(device=moving.device)
         side.wait_stream(torch.cuda.current_stream(moving.device))
         with torch.cuda.stream(side):
             # with step batching the first pass of a shape only RECORDS the packing jobs: a second pass must launch the
             # batched packing kernels (and read the arena) once before they can be captured
             for _ in range(max(warmup, 2 if self.batch_small_launches else 1)):
-                self._fwd_bwd(*self._static_in)
+                self._fwd_bwd(*self._static_in, self._static_labels)
         torch.cuda.current_stream(moving.device).wait_stream(side)
         torch.cuda.synchronize(moving.device)
         self.fp.zero_grad()
@@ -384,7 +426,7 @@ class Trainer:
         import torch.distributed as dist
         mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
         with torch.cuda.graph(g, capture_error_mode=mode):
-            self._static_out = self._fwd_bwd(*self._static_in)
+            self._static_out = self._fwd_bwd(*self._static_in, self._static_labels)
         self._graph = g
         self._graph_key = (tuple(moving.shape), moving.device)
         if verify:
@@ -393,19 +435,24 @@ class Trainer:
         return self
 
     def release_graph(self):
-        self._graph = self._static_in = self._static_out = self._graph_key = self._stage_graphs = None
+        self._graph = self._static_in = self._static_out = self._graph_key = self._stage_graphs = self._static_labels = None
 
     def release_steps(self):
         """drop every cached step context (recorded packing jobs + packed-weights arenas) that no captured graph uses"""
         keep = {k: v for k, v in self._steps.items() if self._graph_key is not None and k[:2] == self._graph_key}
         self._steps = keep
 
-    def train_step(self, moving, fixed, epoch=0):
-        """one iteration of train.py:114-133; returns device scalars (no host sync)"""
+    def train_step(self, moving, fixed, epoch=0, labels=None):
+        """one iteration of train.py:114-133; returns device scalars (no host sync): (loss, sim, reg), and with a ``seg`` term,
+        which needs ``labels = (moving_labels, fixed_labels)``, (loss, sim, reg, seg)"""
+        labels = self._labels(labels, "train_step")
         self.model.train()
         if getattr(self, "_graph", None) is not None and self._graph_key == (tuple(moving.shape), moving.device):
             self._static_in[0].copy_(moving, non_blocking=True)
             self._static_in[1].copy_(fixed, non_blocking=True)
+            if labels is not None:
+                self._static_labels[0].copy_(labels[0], non_blocking=True)
+                self._static_labels[1].copy_(labels[1], non_blocking=True)
             if self._stage_graphs is not None:              # overlapped: replay k -> all-reduce of bucket k (async) -> replay k + 1
                 self.buckets.begin_staged()
                 for k, gr in enumerate(self._stage_graphs):
@@ -415,19 +462,19 @@ class Trainer:
             else:
                 self._graph.replay()
                 scale = self.fp.allreduce_grads(self.group)
-            loss, sim, reg = self._static_out
+            out = self._static_out
         elif self.buckets is not None:
             self.buckets.begin_staged()
-            loss, sim, reg = self._fwd_bwd_staged(moving, fixed, self.buckets.launch)
+            out = self._fwd_bwd_staged(moving, fixed, self.buckets.launch)
             scale = self.buckets.finish_staged()
         else:
-            loss, sim, reg = self._fwd_bwd(moving, fixed)
+            out = self._fwd_bwd(moving, fixed, labels)
             scale = self.fp.allreduce_grads(self.group)
         self.step += 1
         self.lr_last = poly_lr(epoch, self.max_epoch, self.lr0)
         ops.adam_amsgrad_step_(self.fp.flat, self.fp.grad, self.m, self.v, self.vmax, self.lr_last, self.step,
                                self.betas[0], self.betas[1], self.eps, scale)
-        return loss, sim, reg
+        return out
 
     # ---------------------------------------------------------------- optimizer state, torch.optim.Adam's format
     def state_dict(self):

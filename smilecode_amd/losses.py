@@ -2,7 +2,8 @@
 (ModeT/losses.py:6-94), computed by the HIP kernels of csrc/losses.hip; ``MIND_loss`` (Baseline methods/RCN/losses.py:333-399)
 by those of csrc/mind.hip; ``MutualInformation`` and ``localMutualInformation`` (the same file, 401-556) by those of csrc/mi.hip;
 ``SSIM3D`` and ``ssim3D`` (the same file, 103-148) by those of csrc/ssim.hip; ``Grad3DiTV`` and ``DisplacementRegularizer``
-(the same file, 203-268) by those of csrc/reg.hip."""
+(the same file, 203-268) by those of csrc/reg.hip; ``LabelDice``, the label-overlap term of weakly supervised training, by those of
+csrc/segdice.hip."""
 from __future__ import annotations
 
 from functools import partial
@@ -222,15 +223,42 @@ class DisplacementRegularizer(torch.nn.Module):
         return ops.reg_value_and_grad_cl(flow_cl, self.energy_type, grad_scale)
 
 
+class LabelDice(torch.nn.Module):
+    """1 - mean soft Dice over the labels 1..``nlabels`` of the moving label map warped TRILINEARLY by the flow against the fixed
+    one: the overlap term of weakly supervised training, the differentiable form of the Dice that ``infer`` reports (reference
+    utils.py:86-106 for the score and its 1e-5).  ``flow`` (B,3,D,H,W) float32, label maps (B,1,D,H,W) int16; the gradient is
+    with respect to the flow.  No one-hot volume exists at any point (csrc/segdice.hip)."""
+
+    def __init__(self, nlabels=54):
+        super().__init__()
+        if isinstance(nlabels, bool) or not isinstance(nlabels, int) or not 1 <= nlabels <= ops.SEGDICE_MAX_LABELS:
+            raise RuntimeError(f"LabelDice: nlabels must be an integer in 1..{ops.SEGDICE_MAX_LABELS}, got {nlabels!r}")
+        self.nlabels = nlabels
+
+    def forward(self, flow, moving_labels, fixed_labels):
+        if not torch.is_tensor(flow) or flow.dim() != 5 or flow.shape[1] != 3:
+            raise RuntimeError(f"LabelDice: expects a planar (B,3,D,H,W) flow, got "
+                               f"{tuple(flow.shape) if torch.is_tensor(flow) else type(flow)}")
+        return ops.seg_dice_loss(moving_labels, flow.contiguous(), fixed_labels, self.nlabels)
+
+    def seedable(self):
+        return True
+
+    def value_and_grad_cl(self, flow_cl, moving_labels, fixed_labels, grad_scale, d_flow_add=None):
+        return ops.seg_dice_value_and_grad_cl(flow_cl, moving_labels, fixed_labels, self.nlabels, grad_scale, d_flow_add)
+
+
 def seeds(term):
     """the step may start its backward from the term's own gradient (``value_and_grad`` of a similarity term,
-    ``value_and_grad_cl`` of a regulariser): the term is, by exact type, one of the classes of SIM_TERMS / REG_TERMS below, and
-    says that this configuration is seedable.  A subclass or a foreign module goes through autograd."""
-    known = set(SIM_TERMS.values()) | {getattr(make, "func", make) for make in REG_TERMS.values()}
+    ``value_and_grad_cl`` of a regulariser or a label term): the term is, by exact type, one of the classes of SIM_TERMS /
+    REG_TERMS / SEG_TERMS below, and says that this configuration is seedable.  A subclass or a foreign module goes through
+    autograd."""
+    known = set(SIM_TERMS.values()) | {getattr(make, "func", make) for make in REG_TERMS.values()} | set(SEG_TERMS.values())
     return type(term) in known and term.seedable()
 
 
-# the terms by the names train.py's --sim and --reg know: name -> what builds the term with the script's settings
+# the terms by the names train.py's --sim, --reg and --seg know: name -> what builds the term with the script's settings
 SIM_TERMS = {"ncc": NCC_vxm, "mind": MIND_loss, "mi": MutualInformation, "lmi": localMutualInformation, "ssim": SSIM3D}
 REG_TERMS = {"grad3d": partial(Grad3d, penalty="l2"), "itv": Grad3DiTV, "gradient-l2": partial(DisplacementRegularizer, "gradient-l2"),
              "gradient-l1": partial(DisplacementRegularizer, "gradient-l1"), "bending": partial(DisplacementRegularizer, "bending")}
+SEG_TERMS = {"dice": LabelDice}

@@ -2798,6 +2798,85 @@ def reg_loss(flow, kind):
     return _FlowTerm.apply(flow, _reg_launch, (kind, dims, False))
 
 
+# ------------------------------------------------------------------------------------------------ label overlap (soft Dice)
+SEGDICE_MAX_LABELS = 256         # MODET_SEGDICE_MAX_LABELS of include/modet_hip_segdice.h
+# per voxel of one call with a gradient, computed from the shapes (csrc/segdice.hip): the sums pass reads
+# the flow (12 B) and the fixed label (2 B), the gradient pass both again and writes d_flow (12 B); the eight gathered moving
+# labels of either pass come through the caches (2 B of the map per voxel and pass)
+SEGDICE_BYTES_PER_VOXEL = (12.0 + 2.0 + 2.0) + (12.0 + 2.0 + 2.0 + 12.0)
+
+
+def _segdice_args(op, mov_lab, flow, fix_lab, nlabels, channels_last):
+    """(B, D, H, W) of two (B,1,D,H,W) int16 label maps and a planar (B,3,D,H,W) or channels-last (B,D,H,W,3) float32 flow"""
+    if isinstance(nlabels, bool) or not isinstance(nlabels, int) or not 1 <= nlabels <= SEGDICE_MAX_LABELS:
+        raise RuntimeError(f"{op}: nlabels must be an integer in 1..{SEGDICE_MAX_LABELS}, got {nlabels!r}")
+    for name, t in (("mov_lab", mov_lab), ("fix_lab", fix_lab)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{op}: {name} must live on the GPU (the HIP path has no CPU fallback)")
+        if t.dtype != torch.int16:
+            raise RuntimeError(f"{op}: {name} must be int16, got {t.dtype}: convert the label map with .to(torch.int16)")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{op}: {name} must be contiguous")
+    _chk(flow)
+    _pair_shapes(op, mov_lab, fix_lab, "mov_lab", "fix_lab")
+    B, _, D, H, W = mov_lab.shape
+    want = (B, D, H, W, 3) if channels_last else (B, 3, D, H, W)
+    if flow.dim() != 5 or tuple(flow.shape) != want:
+        raise RuntimeError(f"{op}: expects a {'channels-last (B,D,H,W,3)' if channels_last else 'planar (B,3,D,H,W)'} flow "
+                           f"{want} for labels {tuple(mov_lab.shape)}, got {tuple(flow.shape)}")
+    for name, t in (("mov_lab", mov_lab), ("fix_lab", fix_lab)):
+        if t.device != flow.device:
+            raise RuntimeError(f"{op}: {name} lives on {t.device}, the flow on {flow.device}")
+    return B, D, H, W
+
+
+def _segdice_ws(op, flow, dims, nlabels):
+    nb = _L().modet_segdice_ws_bytes(*dims, nlabels)
+    if nb == 0:
+        raise RuntimeError(f"{op}: labels {dims} with {nlabels} labels are out of the kernels' range")
+    # (a float64 tensor: the workspace begins with 64-bit sums)
+    return nb, torch.empty((int(nb) + 7) // 8, dtype=torch.float64, device=flow.device)
+
+
+def _segdice_launch(flow, mov_lab, fix_lab, nlabels, dims, channels_last, want_grad, grad_scale=1.0, d_flow_add=None):
+    """modet_segdice_fwd_bwd: (loss (1,), grad_scale * d loss / d flow in the flow's layout or None, table (B,3,L+1) float64);
+    ``d_flow_add``: the gradient is added into this buffer, which is returned"""
+    nb, ws = _segdice_ws("seg_dice_loss", flow, dims, nlabels)
+    loss = torch.empty(1, dtype=torch.float32, device=flow.device)
+    table = torch.empty((dims[0], 3, nlabels + 1), dtype=torch.float64, device=flow.device)
+    df = d_flow_add if d_flow_add is not None else (torch.empty_like(flow) if want_grad else None)
+    n = float(flow.numel()) / 3
+    with _Guard(flow, f"segdice[{nlabels}]", 120.0 * n, (SEGDICE_BYTES_PER_VOXEL if df is not None else 16.0) * n):
+        _call(_L().modet_segdice_fwd_bwd, _p(mov_lab), _p(flow), _p(fix_lab), _p(loss), _p(table), _p(df), _p(ws), nb, *dims,
+              nlabels, int(bool(channels_last)), float(grad_scale), int(d_flow_add is not None), _stream())
+    return loss, df, table
+
+
+def _segdice_term(flow, mov_lab, fix_lab, nlabels, dims, want_grad):
+    return _segdice_launch(flow, mov_lab, fix_lab, nlabels, dims, False, want_grad)[:2]
+
+
+def seg_dice_loss(mov_lab, flow, fix_lab, nlabels):
+    """1 - mean soft Dice of the moving labels warped trilinearly by a planar flow (B,3,D,H,W) against the fixed labels, both
+    (B,1,D,H,W) int16 with labels 1..nlabels (include/modet_hip_segdice.h has the formulae): the differentiable form of what
+    ``infer`` reports (reference utils.py:86-106, dice_val_VOI).  The gradient is with respect to the flow only."""
+    dims = _segdice_args("seg_dice_loss", mov_lab, flow, fix_lab, nlabels, False)
+    return _FlowTerm.apply(flow, _segdice_term, (mov_lab, fix_lab, nlabels, dims))
+
+
+def seg_dice_sums(mov_lab, flow, fix_lab, nlabels, channels_last=False):
+    """the (B,3,nlabels+1) float64 table [I, P, T] of seg_dice_loss: per batch item and label the overlap, the warped moving and the
+    fixed volume; on an integer-valued flow the counts [2], [0], [1] of label_warp_counts.  Column 0 is 0."""
+    dims = _segdice_args("seg_dice_sums", mov_lab, flow, fix_lab, nlabels, channels_last)
+    nb, ws = _segdice_ws("seg_dice_sums", flow, dims, nlabels)
+    table = torch.empty((dims[0], 3, nlabels + 1), dtype=torch.float64, device=flow.device)
+    n = float(flow.numel()) / 3
+    with _Guard(flow, f"segdice_sums[{nlabels}]", 60.0 * n, 16.0 * n):
+        _call(_L().modet_segdice_sums, _p(mov_lab), _p(flow), _p(fix_lab), _p(table), _p(ws), nb, *dims, nlabels,
+              int(bool(channels_last)), _stream())
+    return table
+
+
 # ------------------------------------------------------------------------------------------------ velocity-field integration
 VECINT_MAX_STEPS = 12       # MODET_VECINT_MAX_STEPS of include/modet_hip_vecint.h
 
@@ -2944,6 +3023,20 @@ def reg_value_and_grad_cl(flow_cl, kind, grad_scale=1.0):
     layout -- no autograd node, no planar copy of the flow: the counterpart of grad3d_value_and_grad_cl"""
     dims = _reg_args("reg_loss", flow_cl, kind, True)
     loss, df = _reg_launch(flow_cl, kind, dims, True, True, grad_scale)
+    return loss.reshape(()), df
+
+
+def seg_dice_value_and_grad_cl(flow_cl, mov_lab, fix_lab, nlabels, grad_scale=1.0, d_flow_add=None):
+    """(seg_dice_loss as a device scalar, grad_scale * d loss / d flow) of a CHANNELS-LAST flow (B,D,H,W,3), gradient in the same
+    layout -- no autograd node.  ``d_flow_add``: a (B,D,H,W,3) buffer the gradient is ADDED into (and which is returned): the
+    step folds this term's seed into the regulariser's without another pass over the flow."""
+    dims = _segdice_args("seg_dice_loss", mov_lab, flow_cl, fix_lab, nlabels, True)
+    if d_flow_add is not None:
+        _chk(d_flow_add)
+        _same_shape("seg_dice_loss", "d_flow_add", d_flow_add, flow_cl.shape, f"flow {tuple(flow_cl.shape)}")
+        if d_flow_add.device != flow_cl.device:
+            raise RuntimeError(f"seg_dice_loss: d_flow_add lives on {d_flow_add.device}, the flow on {flow_cl.device}")
+    loss, df, _ = _segdice_launch(flow_cl, mov_lab, fix_lab, nlabels, dims, True, True, grad_scale, d_flow_add)
     return loss.reshape(()), df
 
 

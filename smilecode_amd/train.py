@@ -4,6 +4,7 @@
     python -m smilecode_amd.train --train-dir /LPBA_path/Train/ --val-dir /LPBA_path/Val/
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m smilecode_amd.train ...
     python -m smilecode_amd.train --synthetic 4 --img-size 64,64,64 --max-epoch 1      # no data needed
+    python -m smilecode_amd.train --seg dice --seg-weight 1 ...        # + the label-overlap term on the training pairs' label maps
     python -m smilecode_amd.train --model im2grid ...      # the Im2Grid baseline ("Baseline methods/Im2Grid/train.py"), its directory name
     python -m smilecode_amd.train --model rdn --channels 16 --levels 1,1,1,1 [--diff] ...   # the RDN baseline ("Baseline methods/RDN/train.py")
     python -m smilecode_amd.train --model rcn --channels 8 --cascades 10 --img-size 192,192,192 ...   # the RCN baseline ("Baseline methods/RCN/train.py")
@@ -24,7 +25,7 @@ import torch
 
 from . import data, utils
 from .engine import Trainer, poly_lr
-from .losses import REG_TERMS, SIM_TERMS
+from .losses import REG_TERMS, SEG_TERMS, SIM_TERMS
 from .models import RCN, RDN, Im2grid, ModeT, PCNet, PRNetplusplus, RDNStages
 from .parallel import init_from_env, lockstep_pairs_for_rank
 
@@ -116,6 +117,12 @@ def make_parser():
                          "DisplacementRegularizer's central-difference gradient norms (gradient-l2, gradient-l1) or bending energy "
                          "(bending), the usual partner of mi and mind")
     ap.add_argument("--reg-weight", type=float, default=1, help="weight of the regulariser in the loss (the reference's weights[1])")
+    ap.add_argument("--seg", choices=tuple(SEG_TERMS), default=None,
+                    help="weakly supervised training: add a label-overlap term on the moving labels warped by the predicted flow against "
+                         "the fixed labels (dice: 1 - mean soft Dice, LabelDice).  The training pairs need label maps: the .pkl files' "
+                         "own (image, labels) or --synthetic's; not with --overlap-allreduce")
+    ap.add_argument("--seg-weight", type=float, default=1, help="weight of the --seg term in the loss")
+    ap.add_argument("--seg-labels", type=int, default=54, help="number of labels 1..N of the --seg term (the label maps' remapped range)")
     ap.add_argument("--diff", action="store_true",
                     help="diffeomorphic variant: every level's field is integrated by scaling and squaring (VecInt) before it is "
                          "composed, as the reference's RDN_diff models do; same parameters, so checkpoints are interchangeable")
@@ -157,6 +164,11 @@ def check_model_args(ap, args):
     """argument combinations a network does not have end as argument errors, before anything is built"""
     if args.model != "rdn" and (getattr(args, "stages", 1) != 1 or getattr(args, "share", False)):
         ap.error("--stages and --share are RDN's (--model rdn): no other network has recursive stages")
+    if getattr(args, "seg", None) is not None:
+        if getattr(args, "overlap_allreduce", False):
+            ap.error("--seg is not built into the staged step of --overlap-allreduce: train it with the plain all-reduce")
+        if not 1 <= getattr(args, "seg_labels", 54) <= 256:
+            ap.error("--seg-labels takes a number of labels in 1..256, got {!r}".format(args.seg_labels))
     if args.model == "im2grid":
         if args.diff:
             ap.error("--diff is ModeT's: the Im2Grid baseline composes its fields without integration")
@@ -263,7 +275,8 @@ def main(argv=None):
             print(ck)
     trainer = Trainer(model, lr=args.lr, max_epoch=args.max_epoch, weights=weights,   # Adam(amsgrad) + NCC + Grad3d('l2')
                       overlap_allreduce=args.overlap_allreduce,
-                      sim=SIM_TERMS[args.sim](), reg=REG_TERMS[args.reg]())
+                      sim=SIM_TERMS[args.sim](), reg=REG_TERMS[args.reg](),
+                      seg=None if args.seg is None else SEG_TERMS[args.seg](args.seg_labels), seg_weight=args.seg_weight)
     if resume is not None and not args.no_restore_optimizer and isinstance(resume.get("optimizer"), dict) \
             and "state" in resume["optimizer"]:
         # the reference saves optimizer.state_dict() but never loads it back (train.py:80-85): a resumed run restarts
@@ -273,20 +286,20 @@ def main(argv=None):
         best_dsc = float(resume.get("best_dsc", 0))         # with or without the optimizer state
 
     if args.synthetic:
-        train_set = data.SyntheticPairs(img_size, args.synthetic, 24)
+        train_set = data.SyntheticPairs(img_size, args.synthetic, 24, with_labels=args.seg is not None)
         val_set = data.SyntheticPairs(img_size, max(2, args.synthetic // 2), 124, with_labels=True)
     else:
-        train_set = data.LPBABrainDatasetS2S(glob.glob(args.train_dir + "*.pkl"))
+        # with --seg the training items are (moving, fixed, labels, labels), the form the validation set has
+        train_set = (data.LPBABrainInferDatasetS2S if args.seg is not None else data.LPBABrainDatasetS2S)(glob.glob(args.train_dir + "*.pkl"))
         val_set = data.LPBABrainInferDatasetS2S(glob.glob(args.val_dir + "*.pkl"))
     # every subject resident in HBM, pairs indexed there; rank 0 alone validates
-    train_cache = None if args.host_loader else data.DeviceVolumeCache(train_set)
+    train_cache = None if args.host_loader else data.DeviceVolumeCache(train_set, with_labels=args.seg is not None)
     val_cache = None if (args.host_loader or rank != 0) else data.DeviceVolumeCache(val_set, with_labels=True)
 
     def train_pair(i):
         if train_cache is not None:
             return train_cache.pair(i)
-        x, y = train_set[i][:2]
-        return x[None].pin_memory().cuda(non_blocking=True), y[None].pin_memory().cuda(non_blocking=True)
+        return tuple(t[None].pin_memory().cuda(non_blocking=True) for t in train_set[i][:4 if args.seg is not None else 2])
 
     def val_pairs():
         for i in range(len(val_set)):
@@ -305,10 +318,11 @@ def main(argv=None):
         mine = [int(order[i]) for i in lockstep_pairs_for_rank(len(order), rank, world)]
         n_iter = len(mine) if not args.max_iters else min(len(mine), args.max_iters)
         for idx in range(1, n_iter + 1):
-            x, y = train_pair(mine[idx - 1])
+            x, y, *labs = train_pair(mine[idx - 1])
+            labels = tuple(labs) if args.seg is not None else None
             if not args.no_graph and trainer._graph is None and not graph_failed:
                 try:
-                    trainer.capture(x, y)           # forward+backward as one hipGraph from here on (engine.Trainer.capture)
+                    trainer.capture(x, y, labels=labels)    # forward+backward as one hipGraph from here on (engine.Trainer.capture)
                 except RuntimeError as e:           # keep training eagerly (every rank takes the same branch below)
                     trainer.release_graph()
                     graph_failed = True
@@ -319,11 +333,12 @@ def main(argv=None):
                     if int(ok.item()) == 0 and not graph_failed:
                         trainer.release_graph()
                         graph_failed = True
-            loss, sim, reg = trainer.train_step(x, y, epoch=epoch)      # lr = poly_lr(epoch) inside (train.py:117)
+            loss, sim, reg, *seg = trainer.train_step(x, y, epoch=epoch, labels=labels)    # lr = poly_lr(epoch) inside (train.py:117)
             if rank == 0:
                 lv = loss.item()                                        # one host sync per iteration, as train.py:130
                 loss_all.update(lv, y.numel())
-                print("Iter {} of {} loss {:.4f}, Img Sim: {:.6f}, Reg: {:.6f}".format(idx, n_iter, lv, sim.item(), reg.item()))
+                print("Iter {} of {} loss {:.4f}, Img Sim: {:.6f}, Reg: {:.6f}".format(idx, n_iter, lv, sim.item(), reg.item())
+                      + "".join(", Seg: {:.6f}".format(v.item()) for v in seg))
         if rank == 0:
             print("{} Epoch {} loss {:.4f}".format(save_dir, epoch, loss_all.avg))
             print("Epoch {} loss {:.4f}".format(epoch, loss_all.avg), file=f, end=" ")
